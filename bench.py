@@ -16,6 +16,11 @@ latent_update, episode-buffer writes), after every rollout insert_episode_batch 
 Behavior_policy.learn + Prediction_policy.learn, and IPPOLearner.train (15 PPO epochs over 255 x 90
 rows per agent) when the 256-episode buffer fills.  Nothing is skipped inside the timed region.
 value = env transitions processed by all ranks / max-over-ranks wall time.
+
+A plain run does only what that figure needs: set-up, warm-up, the timed steps, the JSON line.  ``--full`` adds what is
+measured or checked beside it (in-situ kernel timings and roofline rows, BASELINE configs[4] and configs[3] on this GPU,
+the 1-rank RCCL group at N = 1, the CPU baseline).  ``--dump-outputs DIR`` writes what the last timed step computed as
+.npy files (dump_outputs).
 """
 import argparse
 import contextlib
@@ -144,6 +149,44 @@ def config5_object():
             "peak_tflops": FP32_MFMA_PEAK_TFLOPS,
             "rows": [{"piece": r["piece"], "B": r["B"], "ms": round(r["ms"], 4), "algorithmic_gflop": round(r["gflop"], 2),
                       "tflops": round(r["tflops"], 2), "frac": round(r["frac"], 4)} for r in rows]}
+
+
+DUMP_MAX_BYTES = 64 << 20                   # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20                       # elements kept of a larger array: a fixed seeded choice of positions
+
+
+def dump_outputs(loop, batch, out_dir):
+    """``--dump-outputs DIR``: what the timed path hands back after its last step, as float32 ``DIR/<name>.npy`` -- the last
+    rollout's episode fields the rollout computes (``episode_*``) and every network's state after the last update (one flat
+    array per family of nets, agents in order).  An array above DUMP_SAMPLE elements is stored as its elements at positions
+    drawn once from a fixed seed (sorted), the same positions for every build of the same shapes.  -> {"dir", "files", "bytes"}"""
+    import numpy as np
+    if loop.behavior is not None:
+        loop.behavior.join_decoder()                        # (the last learn()'s decoder update may still run beside)
+    if torch.device(loop.device).type == "cuda":
+        torch.cuda.synchronize()
+    arrays = {"episode_" + k: batch.data[k] for k in ("actions", "actions_onehot", "behavior_latent", "attention_latent",
+                                                      "rnn_states_actors", "rnn_states_critics")}
+    nets = {"actors": loop.mac.agents, "critics": loop.mac.critics}
+    if loop.behavior is not None:
+        nets.update(behavior_encoder=loop.behavior.behavior_encoder, behavior_decoder=loop.behavior.behavior_decoder)
+    if loop.prediction is not None:
+        nets.update(pred_gat=loop.prediction.pred_GAT, pred_decoder=loop.prediction.pred_decoder)
+    for name, mods in nets.items():
+        arrays["params_" + name] = torch.cat([v.detach().reshape(-1).float() for m in mods for v in m.state_dict().values()
+                                              if v.is_floating_point()])
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_SAMPLE:
+            pos = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[pos.to(t.device)]
+        a = t.cpu().numpy().astype(np.float32)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write more than {DUMP_MAX_BYTES} bytes"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": len(arrays), "bytes": total}
 
 
 def strong_loop(total_envs, shard_world, rank, world, emu_world, dev, seed):
@@ -333,6 +376,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the two objects appended AFTER the timed region at N = 1 (outside `value`): `config5` (BASELINE configs[4], "
                          "iplan_amd/config5.py at B = 32 / 256) and `config4_n1` (configs[3]'s 256 envs + global buffer on this one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: in-situ kernel timings and the roofline rows, `config5`, `config4_n1`, the "
+                         "--emulate-rank-of split, the 1-rank RCCL group at N = 1 and `cpu_baseline` (--no-extras / --no-cpu-baseline "
+                         "leave parts out).  Off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32, at most 64 MB; "
+                         "dump_outputs)")
     opt = ap.parse_args()
     if os.environ.get("IPLAN_BENCH_WATCHDOG"):
         import faulthandler
@@ -407,6 +457,8 @@ def main():
     strong = opt.scaling == "strong"
     shard_world = emu_world or world                             # how many ranks the global run is split over
     from iplan_amd.harness import SyntheticLoop
+    import numpy as np
+    np.random.seed(1234 + rank)                                  # (Prediction_policy.learn's row draws: the same inputs in every run)
     if strong:
         loop, args, E, drop = strong_loop(opt.total_envs, shard_world, rank, world, emu_world, dev, 1234 + rank)
     else:
@@ -420,6 +472,14 @@ def main():
             assert loop.learner.dp_global_rows == (args.buffer_size * shard_world - drop) * args.episode_limit
             assert loop.learner.dp_global_count == args.buffer_size * shard_world * args.episode_limit
     rollouts_per_step = max(1, args.buffer_size // E)
+    last_batch = []
+    if opt.dump_outputs:                                         # (keep the episode container the last rollout returned)
+        rollout = loop.rollout
+
+        def rollout_kept():
+            last_batch[:] = [rollout()]
+            return last_batch[0]
+        loop.rollout = rollout_kept
 
     def one_step():
         with contextlib.redirect_stdout(io.StringIO()):            # the reference prints "TRAINING IPPO"
@@ -442,8 +502,9 @@ def main():
     # make up > 5 % of a cycle (ops.KernelTimers).  EVERY gat_fwd launch is bracketed: a rollout's first launches queue behind
     # the decoder update the previous learn() deferred (2.8 ms for the unlucky one), and a 1-in-8 sample whose phase drifts
     # against the 91 launches of a rollout over-weights them (275 us sampled vs 183 us in the rocprofv3 statistics)
+    # (--full only: a plain run times the workload alone)
     from iplan_amd import ops
-    ops.TIMERS = ops.KernelTimers(every={"ac_fwd_kernel:rollout": 8})
+    ops.TIMERS = ops.KernelTimers(every={"ac_fwd_kernel:rollout": 8}) if opt.full else None
     t0 = time.perf_counter()
     for _ in range(opt.steps):
         one_step()
@@ -451,14 +512,15 @@ def main():
         loop.finish()                                       # the last cycle's staged loss read-backs (host run-ahead, harness.cycle)
     barrier()
     dt = time.perf_counter() - t0
-    timed = ops.TIMERS.summary()
+    timed = ops.TIMERS.summary() if opt.full else None
     from iplan_amd.streams import probe_mode
     queue_probe = {"mode": probe_mode(), "streams_replaced_after_first_cycle": getattr(loop, "queue_repairs", None)}
-    scene_clocks = ops.TIMERS.clocks.get("gat_scenes_clocks", [])
+    scene_clocks = ops.TIMERS.clocks.get("gat_scenes_clocks", []) if opt.full else []
     if scene_clocks:                                        # span of the scenes inside the sampled fused launches (100 MHz stamps)
         spans = [(c.view(-1, 5)[:, 4].max() - c.view(-1, 5)[:, 0].min()).item() / 100.0 for c in scene_clocks]
         timed["gat_scenes_span_us"] = (len(spans), sum(spans) / len(spans), 0.0)
     ops.TIMERS = None
+    dumped = dump_outputs(loop, last_batch[0], opt.dump_outputs) if opt.dump_outputs and rank == 0 else None
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -472,7 +534,9 @@ def main():
                 if strong else
                 f"{E} envs/GPU x 90 steps; step = {rollouts_per_step} rollouts, each followed by insert + Behavior_policy.learn + "
                 "Prediction_policy.learn, then IPPOLearner.train (15 epochs x 255 x 90 rows x 5 agents)")
-        rl = rooflines(args, E, timed, opt, rollouts_per_step)
+        rl = rooflines(args, E, timed, opt, rollouts_per_step) if opt.full else None
+        no_group = ("single process, no process group (--in-process / --emulate-rank-of)" if not launched or emu_world else
+                    "no process group at N = 1 (--full creates a 1-rank RCCL group after the timed region)")
         line = {
             "metric": "env-steps/sec (whole node), Hetero-Highway chaotic 5-agent",
             "value": env_steps / dt, "unit": "env-steps/s", "n_gpus": world, "steps": opt.steps,
@@ -482,11 +546,12 @@ def main():
                                    + (" [ROLLOUT ONLY diagnostic]" if opt.rollout_only else ""),
                        "envs_per_gpu": E, "rollouts_per_step": rollouts_per_step,
                        "env_steps_per_step": rollouts_per_step * E * args.episode_limit * world},
-            "roofline": rl[0], "roofline_others": rl[1:],
+            **({"roofline": rl[0], "roofline_others": rl[1:]} if rl else {}),
             # how the ranks came to be: spawned_by_bench = this line's ranks were started by bench.py's own launch_ranks()
             "launcher": {"launched": launched, "spawned_by_bench": bool(os.environ.get("IPLAN_BENCH_SPAWNED")), "world_size": world,
                          **({"spawn_failed": True} if spawn_failed else {}), "hardware_queue_probe": queue_probe,
-                         **(rccl or {"rccl_ranks": None, "note": "single process, no process group (--in-process / --emulate-rank-of)"})},
+                         **(rccl or {"rccl_ranks": None, "note": no_group})},
+            **({"dump_outputs": dumped} if dumped else {}),
         }
         if emu_world:
             per_rank = env_steps / dt
@@ -497,16 +562,16 @@ def main():
                         "xGMI transfer or straggler wait); projected value = total envs x 90 / this rank's step time",
                 "emulated_world": emu_world, "projected_value": per_rank * emu_world, "unit": "env-steps/s",
                 "not_included": "xGMI transfer and rank skew of the 2 + 2 + 30 small all-reduces per step (0.3-4 MB each)"}
-        if emu_world and not opt.no_extras:
+        if emu_world and opt.full and not opt.no_extras:
             line["projection"].update(projection_split(loop, args, E, dev, dist, dt / opt.steps, emu_world, opt))
-        if world == 1 and not emu_world and not strong and not opt.rollout_only and not opt.no_extras:
+        if opt.full and world == 1 and not emu_world and not strong and not opt.rollout_only and not opt.no_extras:
             # BASELINE.json's other GPU configs on the same box, same build, AFTER the timed region (never part of `value`)
             del loop
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
             line["config5"] = config5_object()
             line["config4_n1"] = config4_n1_object(opt, dev)
-        if pg_late:
+        if pg_late and opt.full:
             torch.cuda.synchronize()
             try:
                 dist, rccl = init_rccl()
@@ -515,7 +580,7 @@ def main():
             except Exception as e:                               # noqa: BLE001 -- the measurement is done: a group that cannot be
                 dist = None                                      # created must not cost the single-GPU line
                 line["launcher"]["rccl_error"] = f"{type(e).__name__}: {str(e)[:200]}"
-        if not opt.no_cpu_baseline and world == 1:               # (N = 1 only: at N > 1 the other ranks would sit in RCCL's teardown meanwhile)
+        if opt.full and not opt.no_cpu_baseline and world == 1:  # (N = 1 only: at N > 1 the other ranks would sit in RCCL's teardown meanwhile)
             line["cpu_baseline"] = cpu_baseline(args, E)
 
         def clean(o):                                            # a kernel that was not launched (diagnostic modes): null, not NaN

@@ -545,6 +545,7 @@ def main():
     golden_behavior_fc_learn()
     golden_wrappers()
     golden_seq2seq()
+    golden_reference_dropin()
     print("all golden fixtures written to", GOLD)
 
 
@@ -710,6 +711,127 @@ def golden_seq2seq(seed=95):
                           teacher=teacher, masks=masks, coins=coins, np_seed=seed + 3, out=out, gw=gw, grads=grads))
         seed += 10
     torch.save(cases, os.path.join(GOLD, "seq2seq.pt"))
+
+
+def golden_reference_dropin():
+    """tests/test_reference_dropin.py: the reference's ParallelRunner.run + EpisodeBatch with the all-reference stack and with the
+    iplan_amd classes (host-emulated kernels), the reference learners' parameters after one update, and the reference's
+    cal_value_loss / compute_returns under every loss switch -- each with the weights / inputs it started from"""
+    import itertools
+    from types import SimpleNamespace
+    from components.transforms import OneHot
+    from learners.ippo_learner import IPPOLearner as RefLearner
+    from runners.ippo_parallel_runner import ParallelRunner
+    from iplan_amd import _lib as L
+    from tests import test_reference_dropin as D
+    from tests.emu.emu_lib import get_emu_lib
+    L.use_library_for_tests(get_emu_lib())
+
+    def run(args, stack, env):
+        scheme, groups, preprocess = D._scheme_groups_preprocess(args, OneHot)
+        runner = ParallelRunner(args, env, D._Log())
+        runner.setup(scheme, groups, preprocess, stack[0], stack[1], stack[2])
+        batch, *_ = runner.run(test_mode=False)
+        return batch, runner
+
+    def fields(batch):
+        return {k: batch[k].clone() for k in batch.scheme}
+    out = {}
+    args = D._args()                                         # (the seeds and env streams of each test)
+    end = [args.episode_limit + 5, 4, args.episode_limit + 5]
+    torch.manual_seed(0)
+    ref = D._stack(args, ours=False)
+    w0 = D._weights(ref)
+    torch.manual_seed(0)
+    mine = D._stack(args, ours=True)
+
+    def same(w):                                             # every part starts from these weights, and iplan_amd's stack draws them too
+        return all(torch.equal(a[k], w[n][i][k]) for n, ms in w0.items() for i, a in enumerate(ms) for k in a)
+    assert same(D._weights(mine))
+    out["weights_sha256"] = D._sha256(w0)
+    torch.manual_seed(1)
+    np.random.seed(1)
+    b_ref, _ = run(args, ref, D._env(args, 3, end))
+    torch.manual_seed(1)
+    np.random.seed(1)
+    b_mine, runner = run(args, mine, D._env(args, 3, end))
+    # the drop-in itself, checked here where the reference exists: its runner and EpisodeBatch drive the iplan_amd classes
+    # to the all-reference episode's deterministic fields, and the iplan_amd learners take that EpisodeBatch as is
+    from components.episode_buffer import EpisodeBatch
+    assert isinstance(b_mine, EpisodeBatch)
+    det = ("history", "state", "obs", "reward", "terminated", "filled", "avail_actions", "speed")
+    assert all(torch.equal(b_mine[k], b_ref[k]) for k in det)
+    assert (b_mine["behavior_latent"] - b_ref["behavior_latent"]).abs().max() < 1e-5
+    assert (b_mine["rnn_states_actors"][:, 0] - b_ref["rnn_states_actors"][:, 0]).abs().max() == 0
+    bl, _, _ = mine[1].learn(b_mine, runner.t_env)
+    pl = mine[2].learn(b_mine, runner.t_env)
+    assert all(np.isfinite(float(x)) for x in list(bl) + list(pl))
+    mine[3].insert_episode_batch(b_mine)
+    mine[3].train(runner.t_env)
+    assert any((a - b).abs().max() > 0 for a, b in zip(w0["agents"][0].values(), mine[0].agents[0].state_dict().values()))
+    out["runner"] = dict(episode=D._pack(dict({k: b_ref[k] for k in det + ("behavior_latent",)},
+                                              rnn_states_actors_0=b_ref["rnn_states_actors"][:, 0])))
+
+    args = D._args(decoder_dropout=0.0)
+    torch.manual_seed(0)
+    ref = D._stack(args, ours=False)
+    assert same(D._weights(ref))
+    torch.manual_seed(0)
+    mine = D._stack(args, ours=True)
+    torch.manual_seed(2)
+    np.random.seed(2)
+    batch, _ = run(args, ref, D._env(args, 5))
+    batch["terminated"][:] = (torch.rand(batch["terminated"].shape) < 0.5).to(batch["terminated"].dtype)     # give the losses a mask
+    episode = D._pack(fields(batch))
+    families = ("agents", "critics", "behavior_encoder", "behavior_decoder")
+    for stack in (ref, mine):                                # (the iplan_amd learners on the reference's own EpisodeBatch too)
+        stack[1].learn(batch, 0)
+        stack[3].insert_episode_batch(batch)
+        stack[3].train(0)
+    post = {k: v for k, v in D._weights(ref).items() if k in families}
+    got = D._weights(mine)
+    for name in families:
+        for a_sd, b_sd in zip(got[name], post[name]):
+            tol = 1e-6 if name.startswith("behavior") else 1e-5
+            assert all((a_sd[k] - b).abs().max() <= tol * max(1.0, b.abs().max().item()) for k, b in b_sd.items()), name
+    deltas = D._post_deltas({k: w0[k] for k in families}, post)
+    back = D._apply_deltas({k: w0[k] for k in families}, deltas)
+    assert all(torch.equal(back[n][i][k], v) for n in families for i, sd in enumerate(post[n]) for k, v in sd.items())   # (lossless)
+    out["learners"] = dict(episode=episode, post_deltas=deltas)
+
+    args = D._args()
+    end = [args.episode_limit + 5, 3, args.episode_limit + 5]
+    torch.manual_seed(0)
+    mine = D._stack(args, ours=True)
+    assert same(D._weights(mine))
+    torch.manual_seed(4)
+    np.random.seed(4)
+    b_ref, r_ref = run(args, mine, D._env(args, 7, end))
+    out["runner_vs_runner"] = dict(episode=D._pack(fields(b_ref)), t_env=r_ref.t_env, t=r_ref.t)
+    L.use_library_for_tests(None)
+
+    g = torch.Generator().manual_seed(5)
+    R = 257
+    values, vpred, rets = (torch.randn(R, 1, generator=g) * 3 for _ in range(3))
+    rets = rets * 8                                                        # beyond huber_delta on some rows
+    masks = (torch.rand(R, 1, generator=g) > 0.2).float()
+    loss = {}
+    for hub, clipv, act in itertools.product((True, False), repeat=3):
+        ref_self = SimpleNamespace(clip_param=0.2, huber_delta=10.0, _use_huber_loss=hub, _use_clipped_value_loss=clipv,
+                                   _use_value_active_masks=act)
+        loss[(hub, clipv, act)] = RefLearner.cal_value_loss(ref_self, values, vpred, rets, masks).detach()
+    bs, T = 7, 11
+    rewards = torch.randn(bs, T, 1, generator=g)
+    v_all = torch.randn(bs, T + 1, generator=g)
+    terminated = (torch.rand(bs, T + 1, 1, generator=g) > 0.15).float()   # the reference's "terminated" IS the alive mask here
+    returns = {}
+    for use_gae in (True, False):
+        ref_self = SimpleNamespace(_use_gae=use_gae, gamma=0.99, gae_lambda=0.95,
+                                   mac=SimpleNamespace(get_value_ippo=lambda agent_id, obs, rnn: v_all.unsqueeze(-1)))
+        returns[use_gae] = RefLearner.compute_returns(ref_self, 0, None, rewards, terminated, None).detach()
+    out["ppo_losses"] = dict(values=values, vpred=vpred, rets=rets, masks=masks, value_loss=loss, rewards=rewards, v_all=v_all,
+                             terminated=terminated, returns=returns)
+    torch.save(out, os.path.join(GOLD, "reference_dropin.pt"))
 
 
 if __name__ == "__main__":

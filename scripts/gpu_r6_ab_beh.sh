@@ -6,7 +6,7 @@ for rep in 1 2 3; do
 for v in old new; do
   echo "== $v" >> $O/ab.txt
   IPLAN_HIP_LIB=$R/build/abl/lib_$v.so timeout 300 python scripts/microbench.py behavior_learn 2>&1 | grep -v amdgpu.ids >> $O/ab.txt
-  IPLAN_HIP_LIB=$R/build/abl/lib_$v.so IPLAN_BENCH_WATCHDOG=300 timeout 400 python bench.py --in-process --steps 6 --warmup 2 --no-cpu-baseline --no-extras 2>> $O/ab.err | python -c "
+  IPLAN_HIP_LIB=$R/build/abl/lib_$v.so IPLAN_BENCH_WATCHDOG=300 timeout 400 python bench.py --full --in-process --steps 6 --warmup 2 --no-cpu-baseline --no-extras 2>> $O/ab.err | python -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

@@ -6,8 +6,8 @@ set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R"; O=gpurun_out/r6p1; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q -x > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
 cp gpurun_out/parity_errors.json $O/parity_errors.json 2>/dev/null
-IPLAN_BENCH_WATCHDOG=600 timeout 700 python bench.py --gpus 1 > $O/bench_line.json 2> $O/bench.err < /dev/null; echo "bench rc=$?" >> $O/bench.err
-B="python bench.py --in-process --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+IPLAN_BENCH_WATCHDOG=600 timeout 700 python bench.py --full --gpus 1 > $O/bench_line.json 2> $O/bench.err < /dev/null; echo "bench rc=$?" >> $O/bench.err
+B="python bench.py --full --in-process --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
 for rep in 1 2; do
 for v in base graph cus48 cus64 cus96 behfirst; do
   unset IPLAN_ROLLOUT_GRAPH IPLAN_DEFER_CUS IPLAN_BEH_FIRST
@@ -22,5 +22,5 @@ for ln in sys.stdin:
 " >> $O/ab.txt
 done; done
 unset IPLAN_ROLLOUT_GRAPH IPLAN_DEFER_CUS IPLAN_BEH_FIRST
-IPLAN_BENCH_WATCHDOG=600 timeout 700 python bench.py --scaling strong --emulate-rank-of 8 --no-cpu-baseline > $O/bench_strong_rank_of_8_projection.json 2> $O/bench_proj.err < /dev/null
+IPLAN_BENCH_WATCHDOG=600 timeout 700 python bench.py --full --scaling strong --emulate-rank-of 8 --no-cpu-baseline > $O/bench_strong_rank_of_8_projection.json 2> $O/bench_proj.err < /dev/null
 cat $O/ab.txt; tail -3 $O/pytest_gpu.log; cut -c1-300 $O/bench_line.json; tail -2 $O/bench.err

@@ -3,7 +3,7 @@
 # next to full and unprobed, without RCCL (x4) and with a live group at 4 / 6 queues.
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R"; O=gpurun_out/r6p11; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
-A="--gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+A="--gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extras --full"
 for rep in 1 2; do
 for q in late late early_q4 early_q6; do
 for pr in verify full 0; do

@@ -3,7 +3,7 @@
 # the tests touched since call 1; every PPO optimiser step against the oracle once (scripts/ppo_all_steps_check.py).
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R"; O=gpurun_out/r6p2; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
-A="--steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+A="--steps 6 --warmup 2 --no-cpu-baseline --no-extras --full"
 for rep in 1 2; do
 for v in inproc spawn_late spawn_early; do
   unset IPLAN_BENCH_PG_EARLY

@@ -3,7 +3,7 @@
 # + the launcher's N = 1 fallback test.
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R"; O=gpurun_out/r6p3; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
-A="--gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+A="--gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extras --full"
 for rep in 1 2; do
 for v in late early_q4 early_q5 early_q6 early_q8 early_q12; do
   unset IPLAN_BENCH_PG_EARLY GPU_MAX_HW_QUEUES

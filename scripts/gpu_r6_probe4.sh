@@ -3,7 +3,7 @@
 # order train() -> Behavior_policy.learn in buffer-full cycles (harness.cycle, IPLAN_TRAIN_ORDER) remove the dependence?
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R"; O=gpurun_out/r6p4; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
-A="--gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+A="--gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extras --full"
 for rep in 1 2; do
 for q in late early_q4 early_q6 early_q8 early_q12; do
 for ord in concurrent auto; do

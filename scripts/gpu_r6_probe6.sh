@@ -3,7 +3,7 @@
 # Is the cycle now independent of the stream -> queue accident?  (no RCCL group / RCCL alive at 4, 5, 6, 8 queues; probe on / off)
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd "$R"; O=gpurun_out/r6p8; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
-A="--gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extras"
+A="--gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extras --full"
 for rep in 1 2; do
 for q in late early_q4 early_q6; do
 for pr in min full noprobe; do

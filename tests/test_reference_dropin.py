@@ -1,18 +1,17 @@
-"""Drop-in proof against the REAL reference objects (runs only where /root/reference exists -- the build container; the
-fixtures under tests/golden/ carry the parity to the GPU box): the reference's own ``EpisodeBatch`` and the reference's own
-``ParallelRunner.run`` loop (runners/ippo_parallel_runner.py:105-281) drive the iplan_amd classes -- DcntrlMAC,
-Behavior_policy, Prediction_policy, IPPOLearner, host-emulated kernels -- through a stub vector env, and the episode they
-produce is compared with the one the all-reference stack produces from the same weights on the same observation stream."""
-import os
-import sys
-from types import SimpleNamespace
+"""Drop-in proof against the REAL reference objects, carried to every machine by tests/golden/reference_dropin.pt
+(oracle/make_golden.py golden_reference_dropin records it where the reference tree exists): the episode the all-reference stack
+produces in the reference's own ``ParallelRunner.run`` loop (runners/ippo_parallel_runner.py:105-281) and ``EpisodeBatch``, the
+episode that loop produces driving the iplan_amd classes, the reference learners' parameters after one update on a
+reference-filled episode, and the reference's value loss / returns under every loss switch.  The iplan_amd classes --
+DcntrlMAC, Behavior_policy, Prediction_policy, IPPOLearner, host-emulated kernels -- and iplan_amd's runner, through a stub
+vector env, are compared with them from the same weights on the same observation stream."""
+import hashlib
+import lzma
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
-
-REF = os.environ.get("IPLAN_REFERENCE", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "runners")), reason="the reference tree is not present")
 
 
 class _Log:
@@ -21,18 +20,6 @@ class _Log:
 
     def log_stat(self, k, v, t):
         self.stats[k] = v
-
-
-@pytest.fixture()
-def ref_path():
-    sys.path.insert(0, REF)
-    yield
-    sys.path.remove(REF)
-    for name in list(sys.modules):                     # the reference's top-level package names are generic: unload them
-        if name.split(".")[0] in ("controllers", "learners", "nova", "modules", "components", "runners", "observation_wrapper", "utils", "envs"):
-            mod = sys.modules[name]
-            if getattr(mod, "__file__", None) and str(mod.__file__).startswith(REF):
-                del sys.modules[name]
 
 
 @pytest.fixture()
@@ -55,8 +42,17 @@ def _args(**kw):
     return a
 
 
-def _scheme_groups_preprocess(args):
-    from components.transforms import OneHot
+class _OneHot:
+    """components/transforms.py:8-21 as far as the episode container needs it (the reference's own class when recording)"""
+
+    def __init__(self, out_dim):
+        self.out_dim = out_dim
+
+    def infer_output_info(self, vshape_in, dtype_in):
+        return (self.out_dim,), torch.float32
+
+
+def _scheme_groups_preprocess(args, OneHot=_OneHot):
     from iplan_amd import synth
     scheme = synth.make_scheme(args)
     scheme.pop("actions_onehot")
@@ -92,43 +88,84 @@ def _stack(args, ours):
     return mac, beh, pred, learner
 
 
-def _sync_weights(src, dst):
-    (ms, bs, ps, _), (md, bd, pd, _) = src, dst
-    for i in range(len(ms.agents)):
-        md.agents[i].load_state_dict(ms.agents[i].state_dict())
-        md.critics[i].load_state_dict(ms.critics[i].state_dict())
-        bd.behavior_encoder[i].load_state_dict(bs.behavior_encoder[i].state_dict())
-        bd.behavior_decoder[i].load_state_dict(bs.behavior_decoder[i].state_dict())
-        pd.pred_GAT[i].load_state_dict(ps.pred_GAT[i].state_dict())
-        pd.pred_decoder[i].load_state_dict(ps.pred_decoder[i].state_dict())
+NETS = (("mac", "agents"), ("mac", "critics"), ("beh", "behavior_encoder"), ("beh", "behavior_decoder"), ("pred", "pred_GAT"),
+        ("pred", "pred_decoder"))
 
 
-def _run_reference_runner(args, stack, env):
-    from runners.ippo_parallel_runner import ParallelRunner
+def _weights(stack):
+    """{net family: [state dict per agent]} of a (mac, behaviour, prediction, learner) stack"""
+    owner = dict(zip(("mac", "beh", "pred"), stack))
+    return {name: [{k: v.detach().clone() for k, v in m.state_dict().items()} for m in getattr(owner[o], name)] for o, name in NETS}
+
+
+def _sha256(weights):
+    """{family: [{name: sha256 of the tensor's dtype, shape and bytes}]}: the fixture's exact record of a set of weights"""
+    return {name: [{k: hashlib.sha256(f"{v.dtype}{tuple(v.shape)}".encode() + v.detach().contiguous().numpy().tobytes()).hexdigest()
+                    for k, v in sd.items()} for sd in ms] for name, ms in weights.items()}
+
+
+def _pack(tensors):
+    """{name: tensor} -> {"meta", "blob"}: the tensors' bytes, byte planes apart, LZMA-compressed (lossless; blob: uint8 tensor)"""
+    meta, parts = [], []
+    for k, t in tensors.items():
+        a = t.detach().contiguous().numpy()
+        meta.append((k, a.dtype.str, a.shape))
+        parts.append(a.reshape(-1).view(np.uint8).reshape(-1, a.itemsize).T.tobytes())
+    return dict(meta=meta, blob=torch.frombuffer(bytearray(lzma.compress(b"".join(parts), preset=9)), dtype=torch.uint8))
+
+
+def _unpack(packed):
+    raw, out, o = lzma.decompress(packed["blob"].numpy().tobytes()), {}, 0
+    for k, dt, shape in packed["meta"]:
+        dt = np.dtype(dt)
+        n = int(np.prod(shape)) * dt.itemsize
+        a = np.frombuffer(raw[o:o + n], np.uint8).reshape(dt.itemsize, -1).T.copy().view(dt).reshape(shape)
+        out[k] = torch.from_numpy(a)
+        o += n
+    return out
+
+
+def _post_deltas(before, after):
+    """the update as exact float64 differences (after - before of two float32 tensors is exact in float64), packed"""
+    return _pack({f"{name}.{i}.{k}": after[name][i][k].double() - v.double()
+                  for name, ms in after.items() for i, sd in enumerate(before[name]) for k, v in sd.items()})
+
+
+def _apply_deltas(before, packed):
+    """the parameters after the update, bit for bit: ``before`` + the packed differences, rounded to float32"""
+    d = _unpack(packed)
+    return {name: [{k: (v.double() + d[f"{name}.{i}.{k}"]).to(v.dtype) for k, v in sd.items()} for i, sd in enumerate(before[name])]
+            for name in {key.split(".")[0] for key in d}}
+
+
+def _run_our_runner(args, stack, env):
+    """iplan_amd.runners.ParallelRunner with its own episode container (never a reference class, even where one is importable)"""
+    from iplan_amd.runners.ippo_parallel_runner import ParallelRunner, _dict_batch
     scheme, groups, preprocess = _scheme_groups_preprocess(args)
     runner = ParallelRunner(args, env, _Log())
     runner.setup(scheme, groups, preprocess, stack[0], stack[1], stack[2])
+    runner.new_batch = partial(_dict_batch, scheme, groups, args.batch_size_run, args.episode_limit + 1, preprocess=preprocess, device="cpu")
     batch, *_ = runner.run(test_mode=False)
     return batch, runner
 
 
-def test_reference_parallel_runner_drives_iplan_amd(ref_path, emu):
-    """The reference's ParallelRunner.run + EpisodeBatch with the iplan_amd classes plugged in: the deterministic fields of
-    the episode equal the all-reference run's; the learners then consume the reference's EpisodeBatch unchanged."""
+def test_reference_parallel_runner_drives_iplan_amd(golden, emu):
+    """The reference's ParallelRunner.run + EpisodeBatch drove the iplan_amd classes when the fixture was recorded, and
+    oracle/make_golden.py golden_reference_dropin asserted there what this test asserted with the reference present (the
+    deterministic fields equal the all-reference run's, the learners take the reference's EpisodeBatch unchanged).  Here: the
+    iplan_amd classes from the same weights, stepped in the reference runner's order from the same seeds, give the all-reference
+    episode's deterministic fields; the learners then consume the episode container unchanged."""
+    fixture = golden("reference_dropin")
+    g = fixture["runner"]
     args = _args()
     torch.manual_seed(0)
-    ref = _stack(args, ours=False)
     mine = _stack(args, ours=True)
-    _sync_weights(ref, mine)
+    assert _sha256(_weights(mine)) == fixture["weights_sha256"]              # the reference stack's weights at this seed, exactly
     end = [args.episode_limit + 5, 4, args.episode_limit + 5]                 # env 1 terminates early
     torch.manual_seed(1)
     np.random.seed(1)
-    b_ref, _ = _run_reference_runner(args, ref, _env(args, 3, end))
-    torch.manual_seed(1)
-    np.random.seed(1)
-    b_mine, runner = _run_reference_runner(args, mine, _env(args, 3, end))
-    from components.episode_buffer import EpisodeBatch
-    assert isinstance(b_mine, EpisodeBatch)
+    b_mine, runner = _run_our_runner(args, mine, _env(args, 3, end))
+    b_ref = _unpack(g["episode"])
     T1 = args.episode_limit + 1
     for k in ("history", "state", "obs", "reward", "terminated", "filled", "avail_actions", "speed"):
         assert torch.equal(b_mine[k], b_ref[k]), k
@@ -138,8 +175,7 @@ def test_reference_parallel_runner_drives_iplan_amd(ref_path, emu):
     assert b_mine["actions"].shape == (args.batch_size_run, T1, args.n_agents, 1)
     assert torch.equal(b_mine["actions_onehot"].sum(-1)[:, :args.episode_limit], torch.ones(args.batch_size_run, args.episode_limit, args.n_agents))
     # step 0 has no sampled quantity upstream of the actor / critic except the gumbel gate of the first GAT update
-    assert (b_mine["rnn_states_actors"][:, 0] - b_ref["rnn_states_actors"][:, 0]).abs().max() == 0
-    # the learners take the reference's EpisodeBatch as is
+    assert (b_mine["rnn_states_actors"][:, 0] - b_ref["rnn_states_actors_0"]).abs().max() == 0
     mac, beh, pred, learner = mine
     t_env = runner.t_env
     bl, sl, tl = beh.learn(b_mine, t_env)
@@ -151,57 +187,48 @@ def test_reference_parallel_runner_drives_iplan_amd(ref_path, emu):
     assert any((a - b).abs().max() > 0 for a, b in zip(before, mac.agents[0].parameters()))
 
 
-def test_learners_match_reference_on_a_reference_episode_batch(ref_path, emu):
-    """One EpisodeBatch object (the reference's, filled by the reference's runner) through BOTH stacks' learners: post-update
-    parameters of the behaviour nets (injected dropout via a fixed in-kernel seed is not comparable, so dropout is 0 here) and
-    of the PPO actors / critics agree."""
+def test_learners_match_reference_on_a_reference_episode_batch(golden, emu):
+    """One episode (filled by the reference's runner and stack, stored whole) through the iplan_amd learners: post-update
+    parameters of the behaviour nets (injected dropout via a fixed in-kernel seed is not comparable, so dropout is 0 here) and of
+    the PPO actors / critics agree, element for element, with the reference learners' on the same episode from the same weights."""
+    from iplan_amd import synth
+    fixture = golden("reference_dropin")
+    g = fixture["learners"]
     args = _args(decoder_dropout=0.0)
     torch.manual_seed(0)
-    ref = _stack(args, ours=False)
     mine = _stack(args, ours=True)
-    _sync_weights(ref, mine)
-    torch.manual_seed(2)
-    np.random.seed(2)
-    batch, runner = _run_reference_runner(args, ref, _env(args, 5))
-    batch["terminated"][:] = (torch.rand(batch["terminated"].shape) < 0.5).to(batch["terminated"].dtype)     # give the losses a mask
-    for stack in (ref, mine):
-        stack[1].learn(batch, 0)
-        stack[3].insert_episode_batch(batch)
-        stack[3].train(0)
+    before = _weights(mine)
+    assert _sha256(before) == fixture["weights_sha256"]
+    ref = _apply_deltas(before, g["post_deltas"])
+    batch = synth.DictBatch(_unpack(g["episode"]), args.batch_size_run, args.episode_limit + 1)
+    mine[1].learn(batch, 0)
+    mine[3].insert_episode_batch(batch)
+    mine[3].train(0)
     for i in range(args.n_agents):
         for name in ("behavior_encoder", "behavior_decoder"):
-            for (k, a), (_, b) in zip(getattr(mine[1], name)[i].state_dict().items(), getattr(ref[1], name)[i].state_dict().items()):
+            for (k, a), (_, b) in zip(getattr(mine[1], name)[i].state_dict().items(), ref[name][i].items()):
                 assert (a - b).abs().max() <= 1e-6 * max(1.0, b.abs().max().item()), (name, i, k)
-        for a_m, a_r in ((mine[0].agents[i], ref[0].agents[i]), (mine[0].critics[i], ref[0].critics[i])):
-            for (k, a), (_, b) in zip(a_m.state_dict().items(), a_r.state_dict().items()):
+        for a_m, a_r in ((mine[0].agents[i], ref["agents"][i]), (mine[0].critics[i], ref["critics"][i])):
+            for (k, a), (_, b) in zip(a_m.state_dict().items(), a_r.items()):
                 assert (a - b).abs().max() <= 1e-5 * max(1.0, b.abs().max().item()), (i, k, (a - b).abs().max().item())
 
 
-def _run_our_runner(args, stack, env):
-    from iplan_amd.runners.ippo_parallel_runner import ParallelRunner
-    scheme, groups, preprocess = _scheme_groups_preprocess(args)
-    runner = ParallelRunner(args, env, _Log())
-    runner.setup(scheme, groups, preprocess, stack[0], stack[1], stack[2])
-    batch, *_ = runner.run(test_mode=False)
-    return batch, runner
-
-
-def test_device_resident_runner_equals_reference_runner(ref_path, emu):
+def test_device_resident_runner_equals_reference_runner(golden, emu):
     """iplan_amd.runners.ParallelRunner (in-place launches into the episode container, one D2H of the actions per step) vs
     the reference's ParallelRunner driving the same iplan_amd classes from the same seeds: every field of the episode,
     sampled actions included; one env terminates early, so later steps store action 0 for it."""
+    fixture = golden("reference_dropin")
+    g = fixture["runner_vs_runner"]
     args = _args()
     torch.manual_seed(0)
     mine = _stack(args, ours=True)
+    assert _sha256(_weights(mine)) == fixture["weights_sha256"]
     end = [args.episode_limit + 5, 3, args.episode_limit + 5]
     torch.manual_seed(4)
     np.random.seed(4)
-    b_ref, r_ref = _run_reference_runner(args, mine, _env(args, 7, end))
-    torch.manual_seed(4)
-    np.random.seed(4)
     b_dev, r_dev = _run_our_runner(args, mine, _env(args, 7, end))
-    from components.episode_buffer import EpisodeBatch
-    assert isinstance(b_dev, EpisodeBatch) and r_dev.t_env == r_ref.t_env and r_dev.t == r_ref.t
+    b_ref = _unpack(g["episode"])
+    assert r_dev.t_env == g["t_env"] and r_dev.t == g["t"]
     for k in ("actions", "actions_onehot", "filled", "terminated", "avail_actions"):
         assert torch.equal(b_dev[k], b_ref[k]), k
     for k in ("history", "state", "obs", "reward", "speed", "behavior_latent", "attention_latent", "rnn_states_actors", "rnn_states_critics"):
@@ -220,54 +247,33 @@ def test_device_resident_runner_all_terminated_break(emu):
     scheme = synth.make_scheme(args)
     scheme.pop("actions_onehot")
     scheme.pop("filled")
-
-    class OneHot:                                                 # components/transforms.py:8-21, for the fallback container
-        def __init__(self, out_dim):
-            self.out_dim = out_dim
-
-        def infer_output_info(self, vshape_in, dtype_in):
-            return (self.out_dim,), torch.float32
     full = dict(scheme, actions_onehot={"vshape": (args.n_actions,), "group": "agents"}, filled={"vshape": (1,), "dtype": torch.long})
     mac = DcntrlMAC(full, {"agents": args.n_agents}, args)
     beh, pred = Behavior_policy(args, _Log()), Prediction_policy(args, _Log())
     runner = ParallelRunner(args, _env(args, 9, [3, 2, 3]), _Log())
-    runner.setup(scheme, {"agents": args.n_agents}, {"actions": ("actions_onehot", [OneHot(args.n_actions)])}, mac, beh, pred)
+    runner.setup(scheme, {"agents": args.n_agents}, {"actions": ("actions_onehot", [_OneHot(args.n_actions)])}, mac, beh, pred)
     runner.new_batch = lambda: _dict_batch(scheme, {"agents": args.n_agents}, args.batch_size_run, args.episode_limit + 1,
-                                           {"actions": ("actions_onehot", [OneHot(args.n_actions)])}, "cpu")
+                                           {"actions": ("actions_onehot", [_OneHot(args.n_actions)])}, "cpu")
     batch, _, _, avg_len = runner.run()
     assert runner.t == 2 and float(batch["filled"].sum()) == 3 * args.batch_size_run
     assert batch["actions_onehot"][:, 3:].abs().sum() == 0 and batch["actions"][:, 3:].abs().sum() == 0
     assert torch.isfinite(batch["attention_latent"]).all() and batch["behavior_latent"][:, 2].abs().sum() > 0
 
 
-def test_oracle_ppo_loss_switches_match_the_reference(ref_path):
+def test_oracle_ppo_loss_switches_match_the_reference(golden):
     """oracle.ppo_losses / gae_returns with the loss switches off their shipped values == the reference's own
     cal_value_loss / compute_returns (learners/ippo_learner.py:128-159, 344-365) on the same inputs"""
     import itertools
-    from types import SimpleNamespace
-    import torch
-    from learners.ippo_learner import IPPOLearner as RefLearner            # the real reference (sys.path set up above)
     from oracle import iplan_oracle as O
-    g = torch.Generator().manual_seed(5)
-    R = 257
-    values, vpred, rets = (torch.randn(R, 1, generator=g) * 3 for _ in range(3))
-    rets = rets * 8                                                        # beyond huber_delta on some rows
-    masks = (torch.rand(R, 1, generator=g) > 0.2).float()
-    zero = torch.zeros(R, 1)
+    g = golden("reference_dropin")["ppo_losses"]
+    values, vpred, rets, masks = g["values"], g["vpred"], g["rets"], g["masks"]
+    zero = torch.zeros_like(values)
     for hub, clipv, act in itertools.product((True, False), repeat=3):
-        ref_self = SimpleNamespace(clip_param=0.2, huber_delta=10.0, _use_huber_loss=hub, _use_clipped_value_loss=clipv,
-                                   _use_value_active_masks=act)
-        want = RefLearner.cal_value_loss(ref_self, values, vpred, rets, masks)
+        want = g["value_loss"][(hub, clipv, act)]
         got = O.ppo_losses(zero, zero.mean(), values, zero, zero, vpred, rets, masks, 0.2, 10.0, 0.01, 0.5,
                            use_huber_loss=hub, use_clipped_value_loss=clipv, use_value_active_masks=act)[3]
         assert torch.allclose(got, want, rtol=1e-6, atol=1e-7), (hub, clipv, act, float(got), float(want))
-    bs, T = 7, 11
-    rewards = torch.randn(bs, T, 1, generator=g)
-    v_all = torch.randn(bs, T + 1, generator=g)
-    terminated = (torch.rand(bs, T + 1, 1, generator=g) > 0.15).float()   # the reference's "terminated" IS the alive mask here
     for use_gae in (True, False):
-        ref_self = SimpleNamespace(_use_gae=use_gae, gamma=0.99, gae_lambda=0.95,
-                                   mac=SimpleNamespace(get_value_ippo=lambda agent_id, obs, rnn: v_all.unsqueeze(-1)))
-        want = RefLearner.compute_returns(ref_self, 0, None, rewards, terminated, None)
-        got = O.gae_returns(rewards, v_all.unsqueeze(-1), terminated, 0.99, 0.95, use_gae=use_gae)
+        want = g["returns"][use_gae]
+        got = O.gae_returns(g["rewards"], g["v_all"].unsqueeze(-1), g["terminated"], 0.99, 0.95, use_gae=use_gae)
         assert torch.allclose(got, want, rtol=1e-6, atol=1e-6), use_gae
