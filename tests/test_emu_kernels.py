@@ -125,35 +125,14 @@ def test_rollout_step_emulated(golden):
 
 
 def test_clip_adam_emulated():
-    from iplan_amd.arena import ParamArena
-    from iplan_amd.optim import FusedAdam, step_all
-    from oracle import iplan_oracle as O
-    torch.manual_seed(0)
-    mods = [torch.nn.Linear(7, 5) for _ in range(3)]
-    arena = ParamArena(mods, "cpu")
-    opts = [FusedAdam([(arena, i)], lr=1e-2, eps=1e-5) for i in range(3)]
-    ref_p = [[p.detach().clone() for p in m.parameters()] for m in mods]
-    ref_m = [[torch.zeros_like(p) for p in ps] for ps in ref_p]
-    ref_v = [[torch.zeros_like(p) for p in ps] for ps in ref_p]
-    for step in (1, 2, 3):
-        grads = [[torch.randn_like(p) * (5.0 if i == 1 else 0.1) for p in ps] for i, ps in enumerate(ref_p)]
-        for i, m in enumerate(mods):
-            for p, gq in zip(m.parameters(), grads[i]):
-                p.grad.copy_(gq)
-        if step < 3:
-            step_all(opts, 1.0)
-        else:
-            for o in opts:
-                o.step(max_norm=1.0)
-        for i in range(3):
-            gl = [x.clone() for x in grads[i]]
-            O.clip_grad_norm(gl, 1.0)
-            for k in range(len(gl)):
-                O.adam_step(ref_p[i][k], gl[k], ref_m[i][k], ref_v[i][k], step, 1e-2, 1e-5)
-            for p, r in zip(mods[i].parameters(), ref_p[i]):
-                assert rel_err(p.detach(), r) < 1e-6
-    sd = opts[0].state_dict()
-    assert set(sd["state"].keys()) == {0, 1} and sd["state"][0]["exp_avg"].shape == (5, 7)
+    from tests.kernel_checks import check_clip_adam
+    check_clip_adam("cpu")
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, (1 << 20) + 3])  # = kernel_checks.ADAM_SIZES
+def test_clip_adam_sizes_emulated(n):
+    from tests.kernel_checks import check_clip_adam_sizes
+    check_clip_adam_sizes("cpu", n)
 
 
 def test_harness_rollout_emulated():

@@ -402,25 +402,8 @@ def test_behavior_learn_with_stability_penalty_vs_oracle_emulated():
 
 def test_adam_weight_decay_emulated():
     """weight_decay != 0 (torch.optim.Adam's L2 form, applied after the clip) against torch.optim.Adam itself"""
-    from iplan_amd.arena import ParamArena
-    from iplan_amd.optim import FusedAdam
-    torch.manual_seed(0)
-    mods = [torch.nn.Linear(6, 4)]
-    ref = torch.nn.Linear(6, 4)
-    ref.load_state_dict(mods[0].state_dict())
-    arena = ParamArena(mods, "cpu")
-    opt = FusedAdam([(arena, 0)], lr=1e-2, eps=1e-5, weight_decay=0.05)
-    topt = torch.optim.Adam(ref.parameters(), lr=1e-2, eps=1e-5, weight_decay=0.05)
-    for step in range(3):
-        grads = [torch.randn_like(p) * 3 for p in ref.parameters()]
-        for p, q, gq in zip(mods[0].parameters(), ref.parameters(), grads):
-            p.grad.copy_(gq)
-            q.grad = gq.clone()
-        opt.step(max_norm=1.0)
-        torch.nn.utils.clip_grad_norm_(ref.parameters(), 1.0)
-        topt.step()
-        for p, q in zip(mods[0].parameters(), ref.parameters()):
-            assert max_rel(p.detach(), q.detach()) < 1e-6
+    from tests.kernel_checks import check_adam_weight_decay
+    check_adam_weight_decay("cpu")
 
 
 def test_ppo_minibatches_vs_oracle_emulated():
