@@ -625,6 +625,45 @@ int iplan_pdec_fwd(const IplanPdecArgs* args, iplan_stream_t stream);
 int iplan_pdec_bwd(const IplanPdecArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Trajectory-prediction inference: Prediction_Decoder.forward(last_state, None, hidden) under .eval()
+ * (nova/prediction_net.py:40-63) -- the chain of iplan_pdec_fwd without teacher forcing and without
+ * dropout, forward only: nothing is recorded for a backward pass.
+ * Rows are (sample s, entity i) = s*N + i; hidden size == 32; d <= 16; n_nets <= IPLAN_MAX_NETS.
+ * The start state and the targets are read in place from an episode buffer: the row of entity i of sample s
+ * of net n starts at element  offset[n][s] + i * ent_stride  of x0 (the start state) and, for the target of
+ * horizon step p < P, at element  offset[n][s] + i * ent_stride + (p + 1) * step_stride  of target; its d
+ * features are contiguous.  The caller guarantees that all of these lie inside the buffers.
+ * Outputs, each optional (NULL = not wanted; at least one is):
+ *   pred     the predicted states
+ *   metrics  per (net, step): sum w * ||delta pos||_2 over columns pos_first .. pos_first + pos_count - 1,
+ *            sum w * sum_c |delta_c| over all d columns, sum w, with delta = target - pred and
+ *            w(row, p) = weight[n][s] * [x0 row's presence column != 0] * [target_p row's presence column != 0]
+ *            (the presence factors are dropped when presence_col < 0).  Reduced in a fixed order: per-tile
+ *            partials in part, then one pass over the tiles -- bit-identical from launch to launch.
+ * Without metrics neither target nor weight is read (target may be NULL).
+ */
+typedef struct {
+    int32_t n_nets, S, N, P, d;
+    const float* x0;            /* base of the start states (e.g. the episode buffer's history field)     */
+    const float* target;        /* base of the targets (usually == x0); only read with metrics            */
+    const int64_t* offset;      /* [n_nets, S] element offset of (sample, entity 0, feature 0)             */
+    int64_t ent_stride;         /* elements between entities                                               */
+    int64_t step_stride;        /* elements between time steps                                             */
+    const float* h0;            /* [n_nets, S*N, 32] GAT output = initial hidden state                     */
+    const float* weight;        /* [n_nets, S] sample weights; NULL = 1                                    */
+    int32_t presence_col;       /* < 0: no presence factors                                                */
+    int32_t pos_first, pos_count;
+    const float* params;        /* decoder arena, IPLAN_DEC_* offsets                                      */
+    int64_t params_s_net;
+    int64_t off[IPLAN_DEC_NPARAM];
+    float* pred;                /* [n_nets, S*N, P, d] or NULL                                             */
+    float* metrics;             /* [n_nets, P, 3] or NULL                                                  */
+    float* part;                /* scratch [n_nets, P, 3, ceil(S*N/16)], needed with metrics               */
+} IplanPredictArgs;
+
+int iplan_predict(const IplanPredictArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Behavior_policy.learn, soft update (nova/stable_behavior_policy.py:161-279): the whole episode of
  * every (env, entity) chain of every agent-net in one forward and one backward launch.
  * Encoder parameters: IPLAN_ENC_* (EncoderRNN); decoder parameters: IPLAN_DEC_* of

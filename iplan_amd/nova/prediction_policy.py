@@ -90,6 +90,104 @@ class Prediction_policy:
         out = out.permute(1, 0, 2, 3)          # [E, nA, N, A] view
         return out.cpu().numpy() if as_np else out
 
+    # ---------------------------------------------------------------------------- inference
+    def predict(self, history_single, attention_hidden, behavior_latent=None, noise=None):
+        """Where will the entities be in the next ``pred_length`` steps?  history_single [E,nA,N,d], attention_hidden
+        [E,nA,N,A], behavior_latent [E,nA,N,Z] -> predicted states [E,nA,N,P,d]: one GAT forward and one decoder launch for
+        all agents, the decoder as ``Prediction_Decoder.forward(last_state, None, hidden)`` runs it under ``.eval()``
+        (nova/prediction_net.py:40-63: autoregressive, no teacher forcing, no dropout).  numpy in -> numpy out; device
+        tensors in -> device tensor out.  ``noise``: pre-drawn gumbel samples [nA,E,N,N-1,2]."""
+        as_np = isinstance(history_single, np.ndarray)
+        hist = _as_dev(history_single, self.device)
+        hid = _as_dev(attention_hidden, self.device)
+        E, nA, N, d = hist.shape
+        if hist.stride(3) != 1:
+            hist = hist.contiguous()
+        lat = None
+        if self.args.GAT_use_behavior:
+            lat = _as_dev(behavior_latent, self.device).permute(1, 0, 2, 3)
+        if noise is None:
+            noise = gumbel_noise((nA, E, N, N - 1, 2), self.device)
+        h0, _ = ops.gat_forward(self.gat_arena, hist.permute(1, 0, 2, 3), lat, hid.permute(1, 0, 2, 3), noise)
+        offset = (torch.arange(nA)[:, None] * hist.stride(1) + torch.arange(E)[None, :] * hist.stride(0)).to(torch.int64)
+        assert int(offset.max()) + (N - 1) * hist.stride(2) + d <= hist.untyped_storage().nbytes() // 4 - hist.storage_offset()
+        out = ops.predict(self.dec_arena, hist, offset.to(self.device), hist.stride(2), 0, h0.reshape(nA, E * N, -1), N,
+                          self.pred_length, d, checked=True)
+        pred = out["pred"].view(nA, E, N, self.pred_length, d).permute(1, 0, 2, 3, 4)
+        return pred.cpu().numpy() if as_np else pred
+
+    def evaluate(self, batch, stride=1, pos=(1, 2), presence_col=0, noise=None, max_samples_per_launch=512, defer=False):
+        """Displacement error of the predictor over an episode batch, dense: every start step t = 0, stride, ... < T - P - 1
+        (T as ``learn`` defines it) of every episode, for all agents.  A sample counts when that agent's ``terminated`` flag
+        is clear at t ... t + P (and ``filled``, where the batch carries it, is set there); a row (entity) counts at horizon
+        step p when its presence column is non-zero at t and at t + p + 1.  ``pos``: the position columns, ``presence_col``:
+        the presence column (< 0: every row counts) -- the defaults are highway's layout after the wrapper strips the id
+        (presence, x, y, vx, vy).  The samples go through the GAT and the decoder in chunks of ``max_samples_per_launch``
+        (the gumbel tensor alone is 119 KB per sample at 55 entities and 5 agents); targets are read in place from the
+        history field, nothing but the three metric sums per (agent, step) is written, and the chunks' sums are added in chunk
+        order.  ``noise``: pre-drawn gumbel samples [nA, E * n_starts, N, N-1, 2] in (episode, start) order; drawn from
+        torch's generator otherwise.  Returns a dict of host arrays after ONE read-back: ``displacement`` [nA, P] (mean
+        ||pos error|| per horizon step), ``ade`` [nA] (mean over steps and rows), ``fde`` [nA] (last step), ``l1`` [nA, P] (mean
+        per row of the summed absolute error over all columns), ``count`` [nA, P] (summed weights); a horizon nothing counts
+        for reports NaN.  ``defer=True``: everything is enqueued and a ``finish()`` callable is returned.  Parameters and
+        optimiser state are not touched."""
+        a, dev = self.args, self.device
+        nA, N, P = self.n_agents, self.max_vehicle_num, self.pred_length
+        history = batch["history"][:, :-1].to(device=dev, dtype=torch.float32)
+        attention = batch["attention_latent"][:, :-1].to(device=dev, dtype=torch.float32)
+        latent = batch["behavior_latent"][:, :-1].to(device=dev, dtype=torch.float32) if a.GAT_use_behavior else None
+        ok = batch["terminated"][:, :-1].to(dev)[..., 0] == 0                     # [E, T, nA]
+        try:
+            filled = batch["filled"]
+        except (KeyError, ValueError):
+            filled = None
+        if filled is not None:
+            ok = ok & (filled[:, :-1].to(dev).reshape(ok.shape[0], ok.shape[1], 1) != 0)
+        E, T = history.shape[:2]
+        d = history.shape[-1]
+        avail_len = T - P - 1
+        assert avail_len >= 1 and stride >= 1 and max_samples_per_launch >= 1, (T, P, stride)
+        assert history.stride(4) == 1
+        starts = torch.arange(0, avail_len, stride)
+        n_t = starts.numel()
+        S_all = E * n_t
+        ei = torch.arange(E).repeat_interleave(n_t)                               # sample = (episode, start), episode-major
+        ti = starts.repeat(E)
+        # element offset of (e, t, agent, entity 0, feature 0) in the history view, per (agent, sample): host arithmetic, so
+        # the bound on what the kernel will read is checked here, without a read-back
+        sE, sT, sA, sN, _ = history.stride()
+        offset = (torch.arange(nA)[:, None] * sA + (ei * sE + ti * sT)[None, :]).to(torch.int64)
+        room = history.untyped_storage().nbytes() // 4 - history.storage_offset()
+        assert int(offset.max()) + (N - 1) * sN + P * sT + d <= room
+        offset = offset.to(dev)
+        ei, ti = ei.to(dev), ti.to(dev)
+        weight = ok.unfold(1, P + 1, 1).all(-1)[ei, ti].to(torch.float32).t().contiguous()      # [nA, S_all]
+        if noise is not None:
+            assert noise.shape == (nA, S_all, N, N - 1, 2), (noise.shape, (nA, S_all, N, N - 1, 2))
+        total = torch.zeros(nA, P, 3, dtype=torch.float32, device=dev)
+        for c0 in range(0, S_all, max_samples_per_launch):
+            c1 = min(S_all, c0 + max_samples_per_launch)
+            e_c, t_c = ei[c0:c1], ti[c0:c1]
+            x0 = history[e_c, t_c].permute(1, 0, 2, 3)                            # the GAT's inputs are gathered (data movement only)
+            att = attention[e_c, t_c].permute(1, 0, 2, 3)
+            lat = latent[e_c, t_c].permute(1, 0, 2, 3) if latent is not None else None
+            nz = noise[:, c0:c1].contiguous().to(dev) if noise is not None else gumbel_noise((nA, c1 - c0, N, N - 1, 2), dev)
+            h0, _ = ops.gat_forward(self.gat_arena, x0, lat, att, nz)
+            out = ops.predict(self.dec_arena, history, offset[:, c0:c1].contiguous(), sN, sT, h0.reshape(nA, (c1 - c0) * N, -1), N, P, d,
+                              want_pred=False, want_metrics=True, weight=weight[:, c0:c1].contiguous(), presence_col=presence_col,
+                              pos=pos, checked=True)
+            total += out["metrics"]
+        staged = AsyncHost(total) if defer else None
+
+        def finish():
+            m = (staged.get() if staged is not None else total.cpu()).numpy().astype(np.float64)      # ONE host read-back
+            count = m[..., 2]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                disp = np.where(count > 0, m[..., 0] / count, np.nan)
+                l1 = np.where(count > 0, m[..., 1] / count, np.nan)
+                ade = np.where(count.sum(1) > 0, m[..., 0].sum(1) / count.sum(1), np.nan)
+            return {"displacement": disp, "ade": ade, "fde": disp[:, -1].copy(), "l1": l1, "count": count}
+        return finish if defer else finish()
 
     # ---------------------------------------------------------------------------- learning
     def _sample(self, n_thread, avail_len):

@@ -887,6 +887,68 @@ def pdec_backward(arena, fwd, lib=None):
     return g_h0
 
 
+def predict(arena, hist, offset, ent_stride, step_stride, h0, N, P, d, want_pred=True, want_metrics=False, target=None, weight=None,
+            presence_col=-1, pos=(1, 2), checked=False, lib=None):
+    """Prediction_Decoder.forward in eval mode (no teacher forcing, no dropout, nothing saved) for all nets, with the start
+    state and the targets read in place.  ``hist``: any fp32 tensor whose storage holds the states (e.g. the episode buffer's
+    history field); ``offset`` int64 [n_nets, S]: element offset, from hist's first element, of (sample, entity 0, feature 0);
+    entity i's row is ``ent_stride`` elements further per entity, the target of horizon step p ``(p + 1) * step_stride``
+    elements further, read from ``target`` (default: ``hist``; only with ``want_metrics``).  h0 [n_nets, S*N, 32] contiguous,
+    ``weight`` [n_nets, S] or None (= 1), ``pos`` = the position columns (consecutive), ``presence_col`` < 0 = no presence factor.
+    Unless ``checked`` (the caller has already done it on the host) the offsets are read back and checked against the storage.
+    Returns dict(pred [n_nets, S*N, P, d] or None, metrics [n_nets, P, 3] or None: sums of w * ||d pos||, w * |d|_1, w)."""
+    lib = _lib(lib)
+    n_nets, S = offset.shape
+    dev = h0.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    assert want_pred or want_metrics
+    assert offset.dtype == torch.int64 and offset.is_contiguous() and offset.device == dev
+    assert hist.dtype == torch.float32 and hist.device == dev
+    assert h0.shape == (n_nets, S * N, 32) and h0.is_contiguous() and h0.dtype == torch.float32
+    assert 1 <= d <= 16 and P >= 1 and 1 <= n_nets <= L.MAX_NETS and ent_stride >= 0 and step_stride >= 0
+    if want_metrics and target is None:
+        target = hist
+    if not want_metrics:
+        target = None
+
+    def room(t):                                            # elements from t's first element to the end of its storage
+        return t.untyped_storage().nbytes() // 4 - t.storage_offset()
+    if not checked:
+        lo, hi = int(offset.min()), int(offset.max())
+        assert lo >= 0 and hi + (N - 1) * ent_stride + d <= room(hist), ("start rows outside hist", lo, hi, room(hist))
+        if target is not None:
+            assert target.dtype == torch.float32 and target.device == dev
+            assert hi + (N - 1) * ent_stride + P * step_stride + d <= room(target), ("target rows outside target", hi, room(target))
+    a = L.PredictArgs()
+    a.n_nets, a.S, a.N, a.P, a.d = n_nets, S, N, P, d
+    a.x0, a.offset, a.ent_stride, a.step_stride, a.h0 = hist.data_ptr(), offset.data_ptr(), ent_stride, step_stride, h0.data_ptr()
+    a.presence_col, a.pos_first, a.pos_count = -1, 0, 1
+    a.params, a.params_s_net = arena.data.data_ptr(), arena.net_stride
+    for i, k in enumerate(L.DEC_PARAM_ORDER):
+        a.off[i] = arena.off(k)
+    out = dict(pred=None, metrics=None)
+    if want_pred:
+        out["pred"] = torch.empty(n_nets, S * N, P, d, **f32)
+        a.pred = out["pred"].data_ptr()
+    part = None
+    if want_metrics:
+        pos = tuple(int(c) for c in pos)
+        assert len(pos) >= 1 and pos == tuple(range(pos[0], pos[0] + len(pos))) and 0 <= pos[0] and pos[-1] < d, pos
+        assert presence_col < d
+        a.target = target.data_ptr()
+        a.presence_col, a.pos_first, a.pos_count = max(presence_col, -1), pos[0], len(pos)
+        if weight is not None:
+            assert weight.shape == (n_nets, S) and weight.dtype == torch.float32 and weight.is_contiguous() and weight.device == dev
+            a.weight = weight.data_ptr()
+        out["metrics"] = torch.empty(n_nets, P, 3, **f32)
+        part = torch.empty(n_nets, P, 3, (S * N + 15) // 16, **f32)
+        a.metrics, a.part = out["metrics"].data_ptr(), part.data_ptr()
+    lib.call("iplan_predict", a, L.current_stream(dev))
+    out["_args"] = a
+    out["_keep"] = (hist, target, offset, h0, weight, part)
+    return out
+
+
 # ---- behaviour learning ---------------------------------------------------------------------------------
 def _beh_pieces(which, default):
     """Window pieces of the behaviour forward / backward pipelines (IPLAN_BEH_PIECES[_FWD|_BWD]: tuning / test knobs)."""

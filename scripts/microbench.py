@@ -110,6 +110,73 @@ if not want or "ac_train_parts" in want:
     g1 = torch.randn(nA, rows, device=dev)
     tm("ac_backward(all)", lambda: ops.ac_backward(fo, loop.mac.actor_arena, loop.mac.critic_arena, g_logp=g1, g_entropy=-1e-6, g_values=g1), n=5)
 
+if "predict" in set(sys.argv[1:]):
+    # inference (iplan_predict, pred + metrics, targets read in place) against the training forward (iplan_pdec_fwd on gathered copies) at
+    # the dense evaluation shape: every start step of every episode = E x (T - P - 1) samples per agent-net; then a whole evaluate()
+    P, T = args.pred_length, args.episode_limit
+    pol = loop.prediction
+    history = batch["history"][:, :-1].float()
+    n_t = T - P - 1
+    S = E * n_t
+    ei, ti = torch.arange(E).repeat_interleave(n_t), torch.arange(n_t).repeat(E)
+    sE, sT, sA, sN, _ = history.stride()
+    offset = (torch.arange(nA)[:, None] * sA + (ei * sE + ti * sT)[None, :]).to(torch.int64).to(dev)
+    h0 = torch.randn(nA, S * N, A, device=dev) * 0.1
+    weight = torch.ones(nA, S, device=dev)
+    ag = torch.arange(nA)[:, None].expand(nA, S)
+    x0 = history[ei[None], ti[None], ag].reshape(nA, S * N, d).contiguous()
+    steps = ti[None, :, None] + 1 + torch.arange(P)[None, None, :]
+    actual = history[ei[None, :, None], steps, ag[:, :, None]].permute(0, 1, 3, 2, 4).reshape(nA, S * N, P, d).contiguous()
+
+    def run_predict():
+        return ops.predict(pol.dec_arena, history, offset, sN, sT, h0, N, P, d, want_pred=True, want_metrics=True, weight=weight, presence_col=0,
+                           checked=True)
+
+    def run_pdec():
+        return ops.pdec_forward(pol.dec_arena, x0, h0, actual, weight, N)
+
+    a_, b_ = run_predict(), run_pdec()
+    torch.cuda.synchronize()
+    print("predict vs pdec_fwd predictions bit-equal:", torch.equal(a_["pred"], b_["pred"]), flush=True)
+    del a_, b_
+
+    def passes(fn, n_pass=7, n=5):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(n_pass):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) / n)
+        return out
+
+    res = {"iplan_predict": [], "iplan_pdec_fwd": []}
+    for _ in range(2):                                     # the two alternate, so a drift of the box hits both
+        res["iplan_predict"] += passes(run_predict)
+        res["iplan_pdec_fwd"] += passes(run_pdec)
+    rows = nA * S * N
+    must = {"iplan_predict": rows * 4 * (A + d + 2 * P * d), "iplan_pdec_fwd": rows * 4 * (A + d + 2 * P * d + P * 256)}
+    for k, v in res.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        print(f"{k:16s} S={S} rows={rows} P={P}: median {med:.4f} ms  min {v[0]:.4f}  max {v[-1]:.4f}  spread {(v[-1] - v[0]) / med * 100:.1f} %  "
+              f"bytes that must move {must[k] / 1e6:.1f} MB -> {must[k] / med / 1e9:.3f} TB/s = {must[k] / med / 1e9 / 8.0 * 100:.1f} % of the 8 TB/s peak", flush=True)
+    nz = gumbel_noise((nA, 512, N, N - 1, 2), dev)
+    g_x0 = history[ei[:512].to(dev), ti[:512].to(dev)].permute(1, 0, 2, 3)
+    g_lat = batch["behavior_latent"][:, :-1].float()[ei[:512].to(dev), ti[:512].to(dev)].permute(1, 0, 2, 3)
+    g_att = batch["attention_latent"][:, :-1].float()[ei[:512].to(dev), ti[:512].to(dev)].permute(1, 0, 2, 3)
+    gat = sorted(passes(lambda: ops.gat_forward(pol.gat_arena, g_x0, g_lat, g_att, nz), n_pass=5, n=3))
+    chunks = (S + 511) // 512
+    print(f"gat_forward of one 512-sample chunk: median {gat[len(gat) // 2]:.3f} ms  (x {chunks} chunks = {gat[len(gat) // 2] * chunks:.2f} ms per evaluate)", flush=True)
+    ev = sorted(passes(lambda: pol.evaluate(batch, defer=True), n_pass=5, n=1))
+    print(f"Prediction_policy.evaluate (stride 1, {S} samples x {nA} agents, chunks of 512): median {ev[len(ev) // 2]:.2f} ms  min {ev[0]:.2f}  max {ev[-1]:.2f}",
+          flush=True)
+
 if "gat_phases12" in set(sys.argv[1:]):           # libraries built with -DGAT_P3_CLOCKS only
     clk = torch.zeros(nA * E, 12, dtype=torch.int64, device=dev)
     ops.gat_forward(loop.prediction.gat_arena, hist, lat, hid, noise, out=out, phase_clocks=clk)
