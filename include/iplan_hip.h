@@ -769,6 +769,43 @@ int iplan_beh_fwd(const IplanBehArgs* args, iplan_stream_t stream);
 int iplan_beh_bwd(const IplanBehArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Behaviour-model inference: the chain of iplan_beh_fwd (soft update) without dropout, forward only -- nothing is
+ * recorded for a backward pass, no seed is consumed.  Every (env, entity) chain of every agent-net starts with
+ * latent = 0, encoder hidden = 0, decoder hidden = 0 and walks the windows j < J = T - 1 - L:
+ *   curr = steps j-L+1 .. j (right-aligned, zero-padded), next = steps j+1 .. j+L
+ *   recon_j = Linear(tanh(GRU64(ReLU(Linear([curr_t, latent_{j-1}]))))),  decoder hidden carried across windows
+ *   latent_j = (1 - coef) latent_{j-1} + coef softmax(out(GRU32(ReLU(Linear(curr_t))))),  encoder hidden carried
+ * rows = E * N; d >= 1, Z >= 1, d + Z <= 16; L >= 1; J >= 1; n_nets <= IPLAN_MAX_NETS.  The history is read in place
+ * through its net / env / step strides (IplanBehArgs' layout).
+ * Outputs, each optional (NULL = not wanted; at least one is):
+ *   latent  the latent after window j's update
+ *   recon   the decoder's output
+ *   sums    per (net, window j, look-ahead step t):  sum_rows mask[e, j+1+t] * sum_c |next - recon|  and
+ *           sum_rows max(||curr - recon||_2 - thres, 0).  Reduced in a fixed order: per-tile partials in part, then one
+ *           pass over the tiles -- bit-identical from launch to launch, no floating-point atomics.
+ * Without sums neither the next steps nor mask are read (mask and part may be NULL).
+ */
+typedef struct {
+    int32_t n_nets, E, N, T, L, d, Z;
+    const float* hist;          /* x(net,e,t,i,c) = hist[net*h_s_net + e*h_s_e + t*h_s_t + i*d + c]      */
+    int64_t h_s_net, h_s_e, h_s_t;
+    const float* mask;          /* [n_nets, E, T]; only read with sums                                   */
+    float coef, thres;          /* soft_update_coef, thres_small_variation                               */
+    const float* enc_params;    /* encoder arena, IPLAN_ENC_* offsets                                    */
+    int64_t enc_s_net;
+    int64_t enc_off[IPLAN_ENC_NPARAM];
+    const float* dec_params;    /* decoder arena, IPLAN_DEC_* offsets                                    */
+    int64_t dec_s_net;
+    int64_t dec_off[IPLAN_DEC_NPARAM];
+    float* latent;              /* [n_nets, rows, J, Z] or NULL                                          */
+    float* recon;               /* [n_nets, rows, J, L, d] or NULL                                       */
+    float* sums;                /* [n_nets, J, L, 2] or NULL                                             */
+    float* part;                /* scratch [n_nets, J, L, 2, ceil(rows/16)], needed with sums            */
+} IplanBehEvalArgs;
+
+int iplan_beh_eval(const IplanBehEvalArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Three-layer perceptron of the FC behaviour ablation (nova/behavior_FC_net.py:6-37, Encoder_3FC / Decoder_3FC):
  *   out = [softmax] (W3 tanh(W2 tanh(W1 x + b1) + b2) + b3)   for n_nets stacked nets, rows per net.
  * off[0..5] = linear_1.weight [H,K0], linear_1.bias, linear_2.weight [H,H], linear_2.bias, out.weight [O,H], out.bias.

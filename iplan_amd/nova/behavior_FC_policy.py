@@ -24,6 +24,13 @@ EPS = 1e-10
 class Behavior_policy(_SoftBehaviorPolicy):
     learn_takes_prepared = False
 
+    def evaluate(self, *args, **kwargs):
+        """Only the soft-update policy has the forward-only evaluation kernel (other window geometry / networks here)."""
+        raise NotImplementedError("evaluate() is implemented for the soft-update Behavior_policy only, not the fully-connected ablation")
+
+    def latent_trace(self, *args, **kwargs):
+        raise NotImplementedError("latent_trace() is implemented for the soft-update Behavior_policy only, not the fully-connected ablation")
+
     def init_behavior_net(self):
         """nova/behavior_FC_policy.py:55-76."""
         a = self.args

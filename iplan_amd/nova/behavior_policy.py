@@ -18,6 +18,13 @@ from .stable_behavior_policy import Behavior_policy as _SoftBehaviorPolicy
 class Behavior_policy(_SoftBehaviorPolicy):
     learn_takes_prepared = False
 
+    def evaluate(self, *args, **kwargs):
+        """Only the soft-update policy has the forward-only evaluation kernel (other window geometry / networks here)."""
+        raise NotImplementedError("evaluate() is implemented for the soft-update Behavior_policy only, not the hard-update ablation")
+
+    def latent_trace(self, *args, **kwargs):
+        raise NotImplementedError("latent_trace() is implemented for the soft-update Behavior_policy only, not the hard-update ablation")
+
     def latent_update(self, history, encoder_hidden, prev_latent, out_latent=None, out_hidden=None):
         """nova/behavior_policy.py:78-115: new latent = softmax(encoder(history)), prev_latent is ignored."""
         as_np = isinstance(history, np.ndarray)

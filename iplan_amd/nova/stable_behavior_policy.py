@@ -155,13 +155,18 @@ class Behavior_policy:
         per-window mask sums (all ranks' in data-parallel runs).  A training loop that enqueues other learners beside ``learn`` calls
         this FIRST and passes the result as ``learn(..., prepared=)``: these few tiny launches otherwise queue behind the other
         learners' kernels at the head of the learn phase."""
+        v = self._episode_views(batch)
+        v["win_norm"] = self._global_window_sums(v["mask"])
+        return v
+
+    def _episode_views(self, batch):
+        """``prepare_learn`` without the (possibly all-reduced) window sums: what ``evaluate`` shares with ``learn``"""
         a, dev = self.args, self.device
         history = batch["history"][:, :-1].to(device=dev, dtype=torch.float32)     # [E, T, nA, N, d]
         term = batch["terminated"][:, :-1].to(dev)                                 # [E, T, nA, 1]
         mask = (1 - term[..., 0]) if a.env == "MPE" else term[..., 0]
         mask = mask.permute(2, 0, 1).to(torch.float32).contiguous()                # [nA, E, T]
-        return dict(batch=batch, history=history, mask=mask, hist=history.permute(2, 0, 1, 3, 4),   # hist: [nA, E, T, N, d] view
-                    win_norm=self._global_window_sums(mask))
+        return dict(batch=batch, history=history, mask=mask, hist=history.permute(2, 0, 1, 3, 4))   # hist: [nA, E, T, N, d] view
 
     def learn(self, batch, t_env, keep=None, defer_decoder=False, defer_readback=False, prepared=None):
         """nova/stable_behavior_policy.py:161-279 for all agents at once: ONE persistent forward launch
@@ -300,6 +305,87 @@ class Behavior_policy:
                     self.logger.log_stat(self.log_prefix + k, v, t_env)
             return beh, stab, total
         return finish if defer_readback else finish()
+
+    # ---------------------------------------------------------------------------- inference
+    def evaluate(self, batch, return_latent=False, return_reconstruction=False, defer=False):
+        """How well the current encoder / decoder reconstruct an episode batch: the forward of ``learn`` run deterministically
+        -- no dropout whatever ``decoder_dropout`` is, no draw from any generator -- and without touching parameters or
+        optimiser state.  Same episode views and mask polarity as ``learn`` (``prepare_learn``); ONE forward-only launch for
+        all agents and all envs (csrc/behavior_eval.hip: nothing is recorded for a backward pass, so there is no env
+        chunking), one host read-back.  Returns a dict of host arrays (float64):
+          behavior_loss, stability_loss, total_loss  [nA]: the three values ``learn`` reports, formed from the kernel's sums
+              as the reference forms them (masked L1 / (sum(mask) + EPS) * d * N per window, clamped distance / E / L, mean
+              over the J = T - 1 - L windows; total = behaviour + behavior_variation_penalty * stability)
+          l1_per_step  [nA, L]: mean absolute error per feature at look-ahead step t over the (env, entity, window) triples
+              whose mask is set; NaN where nothing counts
+          count        [nA, L]: those triples
+          latent         [E, J, nA, N, Z]     (``return_latent``): the intent latent after every window's update
+          reconstruction [E, J, nA, N, L, d]  (``return_reconstruction``): the decoder's output for every window
+        ``defer=True``: everything is enqueued on the current stream and a ``finish()`` callable is returned that does the
+        read-back.  The values are THIS process's own: a data-parallel ``dp`` attachment is not consulted (every rank
+        evaluates the episodes it is given)."""
+        self.join_decoder()
+        v = self._episode_views(batch)
+        mask, hist = v["mask"], v["hist"]
+        nA, E, T, N, d = hist.shape
+        L_win, Z = self.max_history_len, self.latent_dim
+        J = T - 1 - L_win
+        out = ops.beh_eval(self.enc_arena, self.dec_arena, hist, mask, L_win, Z, self.soft_update_coef, self.thres_small_variation,
+                           want_latent=return_latent, want_recon=return_reconstruction, want_sums=True)
+        wn = ops.beh_window_mask_sums(mask, L_win)                                   # [nA, J]: this process's envs only
+        col = mask.sum(dim=1)                                                        # [nA, T]
+        steps = torch.arange(J, device=col.device)[:, None] + 1 + torch.arange(L_win, device=col.device)[None, :]
+        count = col[:, steps].sum(dim=1) * N                                         # [nA, L] (sums of 0/1 flags: exact)
+        pieces = [out["sums"].reshape(-1), wn.reshape(-1), count.reshape(-1)]
+        if return_latent:
+            pieces.append(out["latent"].reshape(-1))
+        if return_reconstruction:
+            pieces.append(out["recon"].reshape(-1))
+        host_dev = torch.cat(pieces)
+        staged = AsyncHost(host_dev) if defer else None
+        penalty = self.behavior_variation_penalty
+
+        def finish():
+            host = (staged.get() if staged is not None else host_dev.cpu()).numpy()      # ONE host read-back
+            at = 0
+
+            def take(*shape):
+                nonlocal at
+                n = int(np.prod(shape))
+                piece = host[at:at + n].reshape(shape)
+                at += n
+                return piece
+            s = take(nA, J, L_win, 2).astype(np.float64)
+            w = take(nA, J).astype(np.float64)
+            cnt = take(nA, L_win).astype(np.float64)
+            beh = (s[..., 0].sum(2) / (w * (N * d) + EPS) * (d * N)).sum(1) / J
+            stab = (s[..., 1].sum(2) / E / L_win).sum(1) / J
+            with np.errstate(divide="ignore", invalid="ignore"):
+                l1 = np.where(cnt > 0, s[..., 0].sum(1) / (cnt * d), np.nan)
+            res = {"behavior_loss": beh, "stability_loss": stab, "total_loss": beh + penalty * stab, "l1_per_step": l1, "count": cnt}
+            if return_latent:
+                res["latent"] = take(nA, E, N, J, Z).transpose(1, 3, 0, 2, 4).copy()
+            if return_reconstruction:
+                res["reconstruction"] = take(nA, E, N, J, L_win, d).transpose(1, 3, 0, 2, 4, 5).copy()
+            return res
+        return finish if defer else finish()
+
+    def latent_trace(self, history):
+        """The intent latent the encoder assigns to every vehicle after every window of an episode: history [E, T, nA, N, d]
+        (the steps ``learn`` sees, i.e. already without the episode's last one) -> [E, J, nA, N, Z], J = T - 1 - L; entry j is
+        the latent after the soft update of window j (steps j-L+1 .. j, zero-padded in front), from latent = 0 and a zero
+        hidden state at j = 0 -- what ``latent_update`` gives when it is driven over the same windows step by step.  numpy in
+        -> numpy out, device tensor in -> device tensor out.  One forward-only launch; no parameter, optimiser or generator
+        state is touched, and a data-parallel ``dp`` attachment is not consulted."""
+        self.join_decoder()
+        as_np = isinstance(history, np.ndarray)
+        h = _as_dev(history, self.device)
+        E, T, nA, N, d = h.shape
+        out = ops.beh_eval(self.enc_arena, self.dec_arena, h.permute(2, 0, 1, 3, 4), None, self.max_history_len, self.latent_dim,
+                           self.soft_update_coef, self.thres_small_variation, want_latent=True, want_recon=False, want_sums=False)
+        J = T - 1 - self.max_history_len
+        lat = out["latent"].reshape(nA, E, N, J, self.latent_dim).permute(1, 3, 0, 2, 4)
+        return lat.cpu().numpy() if as_np else lat
 
     # ---------------------------------------------------------------------------- checkpoints
     def save_models(self, path):

@@ -1081,6 +1081,52 @@ def beh_window_mask_sums(mask, L_win, hard=False):
     return (cs[:, j + 1 + L_win] - cs[:, j + 1]).contiguous()
 
 
+def beh_eval(enc_arena, dec_arena, hist, mask, L_win, Z, coef, thres, want_latent=False, want_recon=False, want_sums=True, lib=None):
+    """The chain of ``beh_forward`` (soft update) without dropout, forward only, for all nets in one launch: nothing is recorded,
+    no seed is drawn, no side stream is used.  hist [n_nets, E, T, N, d] (first three dims may be strided), mask [n_nets, E, T]
+    contiguous (only needed, and only read, with ``want_sums``; None otherwise).  Any d + Z <= 16.
+    Returns dict(latent [n_nets, E*N, J, Z] = the latent after window j's update, recon [n_nets, E*N, J, L, d] = the decoder's
+    output, sums [n_nets, J, L, 2] = per (window, look-ahead step) the masked L1 error sum and the clamped distance sum), None
+    for what was not asked for."""
+    lib = _lib(lib)
+    n_nets, E, T, N, d = hist.shape
+    assert want_latent or want_recon or want_sums, "beh_eval: no output asked for"
+    assert hist.dtype == torch.float32 and hist.stride(4) == 1 and hist.stride(3) == d
+    dev = hist.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    J = T - 1 - L_win
+    rows = E * N
+    a = L.BehEvalArgs()
+    a.n_nets, a.E, a.N, a.T, a.L, a.d, a.Z = n_nets, E, N, T, L_win, d, Z
+    a.hist, a.h_s_net, a.h_s_e, a.h_s_t = hist.data_ptr(), hist.stride(0), hist.stride(1), hist.stride(2)
+    a.coef, a.thres = coef, thres
+    a.enc_params, a.enc_s_net = enc_arena.data.data_ptr(), enc_arena.net_stride
+    for i, k in enumerate(L.ENC_PARAM_ORDER):
+        a.enc_off[i] = enc_arena.off(k)
+    a.dec_params, a.dec_s_net = dec_arena.data.data_ptr(), dec_arena.net_stride
+    for i, k in enumerate(L.DEC_PARAM_ORDER):
+        a.dec_off[i] = dec_arena.off(k)
+    out = dict(latent=None, recon=None, sums=None)
+    part = None
+    Jp = max(J, 0)                                         # (J < 1 is refused by the host check of the entry point, before any launch)
+    if want_latent:
+        out["latent"] = torch.empty(n_nets, rows, Jp, Z, **f32)
+        a.latent = out["latent"].data_ptr()
+    if want_recon:
+        out["recon"] = torch.empty(n_nets, rows, Jp, L_win, d, **f32)
+        a.recon = out["recon"].data_ptr()
+    if want_sums:
+        assert mask is not None and mask.shape == (n_nets, E, T) and mask.is_contiguous() and mask.dtype == torch.float32 and mask.device == dev
+        a.mask = mask.data_ptr()
+        out["sums"] = torch.empty(n_nets, Jp, L_win, 2, **f32)
+        part = torch.empty(n_nets, Jp, L_win, 2, (rows + 15) // 16, **f32)
+        a.sums, a.part = out["sums"].data_ptr(), part.data_ptr()
+    _launch("beh_eval_kernel", lambda: lib.call("iplan_beh_eval", a, L.current_stream(dev)))
+    out["_args"] = a
+    out["_keep"] = (hist, mask, part)
+    return out
+
+
 def beh_backward(enc_arena, dec_arena, fwd, accumulate=False, penalty=0.0, E_norm=0, defer_dec_wgrad=False, lib=None):
     """BPTT of beh_forward's behaviour loss: fills both gradient arenas (``accumulate=True``: adds to them -- launches on
     disjoint env chunks of one batch, normalised by a shared ``win_norm``).

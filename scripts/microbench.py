@@ -177,6 +177,67 @@ if "predict" in set(sys.argv[1:]):
     print(f"Prediction_policy.evaluate (stride 1, {S} samples x {nA} agents, chunks of 512): median {ev[len(ev) // 2]:.2f} ms  min {ev[0]:.2f}  max {ev[-1]:.2f}",
           flush=True)
 
+if "behavior_evaluate" in set(sys.argv[1:]):
+    # behaviour-model inference (iplan_beh_eval, sums only: what evaluate() launches) against the training forward (iplan_beh_fwd with
+    # drop_p = 0: records, carry buffers, encoder / decoder pieces on two streams) on the same episode views, alternating in one process;
+    # then a whole Behavior_policy.evaluate (views, launch, window sums, one read-back) and the peak device memory each adds
+    pol = loop.behavior
+    v = pol.prepare_learn(batch)
+    b_hist, b_mask, b_wn = v["hist"], v["mask"], v["win_norm"]
+    Lw, T = args.max_history_len, args.episode_limit
+    J = T - 1 - Lw
+    tiles = (E * N + 15) // 16
+
+    def run_eval():
+        return ops.beh_eval(pol.enc_arena, pol.dec_arena, b_hist, b_mask, Lw, Z, args.soft_update_coef, args.thres_small_variation)
+
+    def run_train_fwd():
+        return ops.beh_forward(pol.enc_arena, pol.dec_arena, b_hist, b_mask, Lw, Z, args.soft_update_coef, args.thres_small_variation, 0.0,
+                               seed=0, win_norm=b_wn)
+
+    def bpasses(fn, n_pass=5, n=3):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(n_pass):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) / n)
+        return out
+
+    def peak_extra(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        level = torch.cuda.memory_allocated(dev)
+        r = fn()
+        torch.cuda.synchronize()
+        extra = torch.cuda.max_memory_allocated(dev) - level
+        del r
+        return extra
+
+    res = {"iplan_beh_eval": [], "iplan_beh_fwd(drop_p=0)": []}
+    for _ in range(2):                                     # the two alternate, so a drift of the box hits both
+        res["iplan_beh_eval"] += bpasses(run_eval)
+        res["iplan_beh_fwd(drop_p=0)"] += bpasses(run_train_fwd)
+    mem = {"iplan_beh_eval": peak_extra(run_eval), "iplan_beh_fwd(drop_p=0)": peak_extra(run_train_fwd)}
+    # 16-chain tile-steps x (encoder 104 + decoder 416) v_mfma_f32_16x16x4_f32 x 2048 FLOP; fp32 MFMA peak 157.3 TFLOP/s
+    flop = nA * tiles * J * Lw * 520 * 2048.0
+    for k, t in res.items():
+        t = sorted(t)
+        med = t[len(t) // 2]
+        print(f"{k:24s} {nA} nets x {E * N} chains x {J} windows x {Lw} steps: median {med:.3f} ms  min {t[0]:.3f}  max {t[-1]:.3f}  "
+              f"spread {(t[-1] - t[0]) / med * 100:.1f} %  peak extra device memory {mem[k] / 2 ** 20:.1f} MiB"
+              + (f"  {flop / med / 1e9:.1f} TFLOP/s = {flop / med / 1e9 / 157.3 * 100:.1f} % of the fp32 MFMA peak" if k == "iplan_beh_eval" else ""),
+              flush=True)
+    ev = sorted(bpasses(lambda: pol.evaluate(batch), n_pass=5, n=1))
+    print(f"Behavior_policy.evaluate ({E} envs, no optional outputs): median {ev[len(ev) // 2]:.3f} ms  min {ev[0]:.3f}  max {ev[-1]:.3f}  "
+          f"peak extra device memory {peak_extra(lambda: pol.evaluate(batch)) / 2 ** 20:.1f} MiB", flush=True)
+
 if "gat_phases12" in set(sys.argv[1:]):           # libraries built with -DGAT_P3_CLOCKS only
     clk = torch.zeros(nA * E, 12, dtype=torch.int64, device=dev)
     ops.gat_forward(loop.prediction.gat_arena, hist, lat, hid, noise, out=out, phase_clocks=clk)
