@@ -806,6 +806,54 @@ typedef struct {
 int iplan_beh_eval(const IplanBehEvalArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Attention inspection: GAT_Net.forward walked over S >= 1 consecutive steps in one launch, forward only,
+ *   h_s = GAT([src0_s || src1_s], h_{s-1}),   s = 0 .. S-1,   h_{-1} = hidden0 (NULL: zeros),
+ * one workgroup per (net, env) scene; a step's arithmetic is the inference form of iplan_gat_fwd (nothing saved), so the
+ * latents are the ones S successive iplan_gat_fwd launches give.  src0 / src1 are read in place: element (net, b, s, i, c) at
+ * src + net*s_net + b*s_b + s*s_step + i*d + c (views of [E, S, nA, N, .] episode fields).
+ * Outputs, each optional (NULL = not wanted; at least one is), element (net, b, s) at base + net*s_net + b*s_b + s*s_step:
+ *   latent            [N, A]  the attention latent after step s
+ *   soft, hard, attn  [N, N]  ENTITY-indexed maps: [i, j] = softmax weight / gumbel gate / their product that ego i gives
+ *                             entity j (slot j - [j > i] of the backward record's [N, N-1] layout); the diagonal is written as 0
+ *   stats             [n_nets, B, S, 6] contiguous: the scene-step's own sums, with pres(i) = src0 column presence_col of entity i
+ *                     is non-zero at step s (presence_col < 0: every entity), w = weight[net, b, s] (NULL: 1):
+ *                       [0] w * #{i pres}                         [1] w * #{(i, j): i pres, j != i, j pres}
+ *                       [2] w * sum over those pairs of hard      [3] w * sum over those pairs of soft * hard
+ *                       [4] w * sum over those pairs of soft      [5] w * sum_{i pres} -sum_{j != i} soft log soft  (0 log 0 = 0)
+ *                     summed inside the workgroup in a fixed order, no atomics: bit-identical from launch to launch.
+ * noise: gumbel samples [n_nets, B, S, N, N-1, 2] contiguous, or NULL = none (the deterministic gate sigmoid((l1 - l0) / tau)).
+ * hidden0 and latent: 16-byte aligned, strides % 4 == 0.  2 <= N <= IPLAN_MAX_ENTITIES.
+ */
+#define IPLAN_GAT_TRACE_NSTAT 6
+typedef struct {
+    int32_t n_nets, B, N, d0, d1, S;
+    const float* src0;
+    int64_t src0_s_net, src0_s_b, src0_s_step;
+    const float* src1;          /* may be NULL iff d1 == 0                                                 */
+    int64_t src1_s_net, src1_s_b, src1_s_step;
+    const float* hidden0;       /* rows of A floats: (net, b, i) at hidden0 + net*h_s_net + b*h_s_b + i*A; or NULL */
+    int64_t h_s_net, h_s_b;
+    const float* noise;
+    const float* params;        /* parameter arena, IPLAN_GAT_* offsets                                    */
+    int64_t params_s_net;
+    int64_t off[IPLAN_GAT_NPARAM];
+    float tau;
+    int32_t presence_col;
+    const float* weight;        /* [n_nets, B, S] or NULL                                                  */
+    float* latent;
+    int64_t lat_s_net, lat_s_b, lat_s_step;
+    float* soft;
+    int64_t soft_s_net, soft_s_b, soft_s_step;
+    float* hard;
+    int64_t hard_s_net, hard_s_b, hard_s_step;
+    float* attn;
+    int64_t attn_s_net, attn_s_b, attn_s_step;
+    float* stats;
+} IplanGatTraceArgs;
+
+int iplan_gat_trace(const IplanGatTraceArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Three-layer perceptron of the FC behaviour ablation (nova/behavior_FC_net.py:6-37, Encoder_3FC / Decoder_3FC):
  *   out = [softmax] (W3 tanh(W2 tanh(W1 x + b1) + b2) + b3)   for n_nets stacked nets, rows per net.
  * off[0..5] = linear_1.weight [H,K0], linear_1.bias, linear_2.weight [H,H], linear_2.bias, out.weight [O,H], out.bias.

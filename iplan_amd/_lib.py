@@ -52,7 +52,8 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_ac_bwd_tail", "iplan_ac_bwd_fc1", "iplan_ac_bwd_fc1_finalize", "iplan_ppo_prepare", "iplan_ppo_adv_norm", "iplan_ppo_loss", "iplan_gat_bwd",
                 "iplan_pdec_fwd", "iplan_pdec_bwd", "iplan_beh_fwd", "iplan_beh_bwd", "iplan_mlp3_fwd", "iplan_mlp3_bwd", "iplan_seq2seq_fwd", "iplan_ac_pack_fc1",
                 "iplan_ac_xhat_pack", "iplan_ac_fc1_split_fwd", "iplan_ac_bwd_fc1_split",
-                "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval"]
+                "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
+                "iplan_gat_trace"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts"]      # non (args*, stream) signatures
 
@@ -386,6 +387,25 @@ class BehEvalArgs(C.Structure):
     ]
 
 
+GAT_TRACE_NSTAT = 6      # IPLAN_GAT_TRACE_NSTAT
+
+
+class GatTraceArgs(C.Structure):
+    _fields_ = [
+        ("n_nets", i32), ("B", i32), ("N", i32), ("d0", i32), ("d1", i32), ("S", i32),
+        ("src0", fp), ("src0_s_net", i64), ("src0_s_b", i64), ("src0_s_step", i64),
+        ("src1", fp), ("src1_s_net", i64), ("src1_s_b", i64), ("src1_s_step", i64),
+        ("hidden0", fp), ("h_s_net", i64), ("h_s_b", i64),
+        ("noise", fp), ("params", fp), ("params_s_net", i64), ("off", i64 * GAT_NPARAM), ("tau", C.c_float),
+        ("presence_col", i32), ("weight", fp),
+        ("latent", fp), ("lat_s_net", i64), ("lat_s_b", i64), ("lat_s_step", i64),
+        ("soft", fp), ("soft_s_net", i64), ("soft_s_b", i64), ("soft_s_step", i64),
+        ("hard", fp), ("hard_s_net", i64), ("hard_s_b", i64), ("hard_s_step", i64),
+        ("attn", fp), ("attn_s_net", i64), ("attn_s_b", i64), ("attn_s_step", i64),
+        ("stats", fp),
+    ]
+
+
 # ---- FC behaviour ablation -------------------------------------------------------------------------------
 class Mlp3Args(C.Structure):
     _fields_ = [
@@ -421,4 +441,5 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanWgradArgs": WgradArgs, "IplanPpoPrepareArgs": PpoPrepareArgs, "IplanPpoLossArgs": PpoLossArgs,
                   "IplanPdecArgs": PdecArgs, "IplanBehArgs": BehArgs, "IplanMlp3Args": Mlp3Args, "IplanAdvNormArgs": AdvNormArgs, "IplanSeq2SeqArgs": Seq2SeqArgs, "IplanSeq2SeqBwdArgs": Seq2SeqBwdArgs, "IplanAcPackArgs": AcPackArgs,
                   "IplanIpcHandle": IpcHandle, "IplanP2pArgs": P2pArgs, "IplanAcXhatArgs": AcXhatArgs, "IplanAcFc1SplitArgs": AcFc1SplitArgs,
-                  "IplanObsHistArgs": ObsHistArgs, "IplanPredictArgs": PredictArgs, "IplanBehEvalArgs": BehEvalArgs}
+                  "IplanObsHistArgs": ObsHistArgs, "IplanPredictArgs": PredictArgs, "IplanBehEvalArgs": BehEvalArgs,
+                  "IplanGatTraceArgs": GatTraceArgs}

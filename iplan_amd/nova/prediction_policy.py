@@ -189,6 +189,131 @@ class Prediction_policy:
             return {"displacement": disp, "ade": ade, "fde": disp[:, -1].copy(), "l1": l1, "count": count}
         return finish if defer else finish()
 
+    # ---------------------------------------------------------------------------- attention inspection
+    def attention_map(self, history_single, attention_hidden, behavior_latent=None, noise=None, deterministic=False, presence_col=0):
+        """Which neighbours does each agent's GAT attend to at ONE step?  history_single [E,nA,N,d], attention_hidden [E,nA,N,A],
+        behavior_latent [E,nA,N,Z] (ignored without ``GAT_use_behavior``) -> dict of ``attention``, ``soft``, ``hard`` [E,nA,N,N]
+        and ``latent`` [E,nA,N,A].  The maps are indexed by ENTITY: ``[e, a, i, j]`` is what ego i gives entity j -- ``soft`` the
+        softmax weight, ``hard`` the gumbel-softmax gate, ``attention`` their product (the weight the value of j enters the
+        aggregate of i with); the diagonal is 0.  ``latent`` is bit-for-bit what ``GAT_latent_update`` returns for the same
+        inputs and noise.  ``noise``: pre-drawn gumbel samples [nA,E,N,N-1,2], drawn from torch's generator when None;
+        ``deterministic=True`` uses no noise at all (the gate is sigmoid((l1 - l0) / tau)) and draws nothing.  numpy in -> numpy
+        out, device tensors in -> device tensors out.  One launch (``attention_trace``'s kernel with one step); parameters,
+        gradients and optimiser state are not touched."""
+        as_np = isinstance(history_single, np.ndarray)
+        hist = _as_dev(history_single, self.device).unsqueeze(1)
+        hid = _as_dev(attention_hidden, self.device)
+        if self.args.GAT_use_behavior and behavior_latent is None:
+            raise ValueError("attention_map: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
+        lat = _as_dev(behavior_latent, self.device).unsqueeze(1) if self.args.GAT_use_behavior else None
+        if noise is not None and not deterministic:
+            noise = _as_dev(noise, self.device).unsqueeze(2)
+        res = self.attention_trace(hist, lat, hidden0=hid, noise=noise, deterministic=deterministic, want=("attention", "soft", "hard"),
+                                   presence_col=presence_col, max_envs_per_launch=hist.shape[0], _stats=False)
+        out = {k: res[k][:, 0] for k in ("attention", "soft", "hard", "latent")}
+        return {k: v.cpu().numpy() for k, v in out.items()} if as_np else out
+
+    def attention_trace(self, history, behavior_latent=None, hidden0=None, noise=None, deterministic=False, want=("attention",),
+                        weight=None, presence_col=0, max_envs_per_launch=64, defer=False, _stats=True):
+        """How does the attention evolve over an episode?  Walks the GAT over the S steps of ``history`` [E,S,nA,N,d] (with
+        ``behavior_latent`` [E,S,nA,N,Z]; ignored without ``GAT_use_behavior``) from ``hidden0`` [E,nA,N,A] (None: zeros) in one
+        launch per chunk of environments: latent_s = GAT(history_s, behavior_latent_s, latent_{s-1}).  Returns a dict with
+        ``latent`` [E,S,nA,N,A], the maps named in ``want`` (any of ``attention``, ``soft``, ``hard``: [E,S,nA,N,N], indexed by
+        entity as ``attention_map`` describes) and ``stats``, host arrays [nA,S] after ONE read-back:
+          ``gate``               mean gumbel gate over the (ego, neighbour) pairs with both present
+          ``attention_per_ego``  attention mass (soft * hard over those pairs) per present ego
+          ``present_mass``       softmax mass a present ego gives present neighbours (the rest went to empty slots)
+          ``entropy``            entropy of a present ego's softmax over its N-1 neighbours
+          ``egos``, ``pairs``    the weighted counts the means are taken over; a step nothing counts at reports NaN.
+        An entity is present when column ``presence_col`` of its history row is non-zero (< 0: every entity counts); ``weight``
+        [E,S,nA] (e.g. ``1 - terminated`` times ``filled``) weighs every (env, step, agent), None = 1.  The sums over the
+        environments are taken in float64 in environment order, so they do not depend on ``max_envs_per_launch`` (the chunk
+        size: the gumbel tensor is N (N-1) 2 S floats per scene).  ``noise``: pre-drawn gumbel samples [nA,E,S,N,N-1,2]; None
+        draws them from torch's generator as ``GAT_latent_update`` does; ``deterministic=True`` passes no noise and draws
+        nothing.  numpy in -> numpy out, device tensors in -> device tensors out.  ``defer=True``: everything is enqueued and a
+        ``finish()`` callable returning the dict is handed back.  Parameters, gradients and optimiser state are not touched.
+
+        Replaying a rollout (the alignment of ``SyntheticLoop``'s rollout: step t reads the history of t + 1 and the latents of
+        t): with ``b = batch`` and the per-step noise the rollout used, stacked as [nA,E,T,N,N-1,2],
+            ``attention_trace(b["history"][:, 1:], b["behavior_latent"][:, :-1], hidden0=b["attention_latent"][:, 0], noise=...)``
+        gives ``latent == b["attention_latent"][:, 1:]`` bit for bit."""
+        as_np = isinstance(history, np.ndarray)
+        dev = self.device
+        hist = _as_dev(history, dev)
+        E, S, nA, N, d = hist.shape
+        A = self.args.attention_dim
+        assert max_envs_per_launch >= 1
+        want = tuple(want)
+        names = {"attention": "attn", "soft": "soft", "hard": "hard"}
+        assert all(k in names for k in want), want
+        if hist.stride(4) != 1 or hist.stride(3) != d:
+            hist = hist.contiguous()
+        lat = None
+        if self.args.GAT_use_behavior:
+            if behavior_latent is None:
+                raise ValueError("attention_trace: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
+            lat = _as_dev(behavior_latent, dev)
+            if lat.stride(4) != 1 or lat.stride(3) != lat.shape[4]:
+                lat = lat.contiguous()
+            lat = lat.permute(2, 0, 1, 3, 4)
+        src0 = hist.permute(2, 0, 1, 3, 4)                                        # [nA, E, S, N, d] view, read in place
+        h0 = None
+        if hidden0 is not None:
+            h0 = _as_dev(hidden0, dev)
+            if h0.stride(3) != 1 or h0.stride(2) != A or h0.data_ptr() % 16 or h0.stride(0) % 4 or h0.stride(1) % 4:
+                h0 = h0.contiguous()
+            h0 = h0.permute(1, 0, 2, 3)
+        if deterministic:
+            noise = None
+        elif noise is not None:
+            noise = _as_dev(noise, dev)
+            assert noise.shape == (nA, E, S, N, N - 1, 2), (noise.shape, (nA, E, S, N, N - 1, 2))
+        w = None
+        if weight is not None:
+            w = _as_dev(weight, dev)
+            assert w.shape == (E, S, nA), w.shape
+            w = w.permute(2, 0, 1)
+        res = {"latent": torch.empty(E, S, nA, N, A, dtype=torch.float32, device=dev)}
+        for k in want:
+            res[k] = torch.empty(E, S, nA, N, N, dtype=torch.float32, device=dev)
+        parts = []
+        for e0 in range(0, E, max_envs_per_launch):
+            e1 = min(E, e0 + max_envs_per_launch)
+            if deterministic:
+                nz = None
+            elif noise is not None:
+                nz = noise[:, e0:e1].to(device=dev, dtype=torch.float32).contiguous()
+            else:
+                nz = gumbel_noise((nA, e1 - e0, S, N, N - 1, 2), dev)
+            out = {"latent": res["latent"][e0:e1].permute(2, 0, 1, 3, 4)}
+            for k in want:
+                out[names[k]] = res[k][e0:e1].permute(2, 0, 1, 3, 4)
+            got = ops.gat_trace(self.gat_arena, src0[:, e0:e1], None if lat is None else lat[:, e0:e1], None if h0 is None else h0[:, e0:e1],
+                                nz, want=tuple(out) + (("stats",) if _stats else ()), weight=None if w is None else w[:, e0:e1].contiguous(),
+                                presence_col=presence_col, out=out)
+            if _stats:
+                parts.append(got["stats"])
+        sums = torch.cat(parts, dim=1) if _stats else None                        # [nA, E, S, 6]
+        staged = AsyncHost(sums) if (defer and _stats) else None
+
+        def finish():
+            r = {k: (v.cpu().numpy() if as_np else v) for k, v in res.items()}
+            if not _stats:
+                return r
+            m = (staged.get() if staged is not None else sums.cpu()).numpy().astype(np.float64)       # ONE host read-back
+            tot = np.zeros((nA, S, m.shape[-1]))
+            for e in range(E):                                                    # environment order, whatever the chunks were
+                tot += m[:, e]
+            egos, pairs = tot[..., 0], tot[..., 1]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r["stats"] = {"gate": np.where(pairs > 0, tot[..., 2] / pairs, np.nan),
+                              "attention_per_ego": np.where(egos > 0, tot[..., 3] / egos, np.nan),
+                              "present_mass": np.where(egos > 0, tot[..., 4] / egos, np.nan),
+                              "entropy": np.where(egos > 0, tot[..., 5] / egos, np.nan),
+                              "egos": egos, "pairs": pairs}
+            return r
+        return finish if defer else finish()
+
     # ---------------------------------------------------------------------------- learning
     def _sample(self, n_thread, avail_len):
         """The host-side random draws of one agent in the reference's order: the (episode, t) sample of

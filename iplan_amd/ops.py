@@ -116,6 +116,97 @@ def gat_forward(arena, src0, src1, h_prev, noise, tau=0.01, save=False, out=None
     return out, saved
 
 
+def _nbs_strides(t, inner, what):
+    """t is logically [n_nets, B, S, <inner dims contiguous>] with non-negative strides; returns (s_net, s_b, s_step) in elements
+    after checking on the host that the last element the kernel can touch lies inside t's storage."""
+    assert t.dtype == torch.float32, (what, t.dtype)
+    expect = 1
+    for d in range(t.dim() - 1, 2, -1):
+        assert t.stride(d) == expect or t.shape[d] == 1, (what, t.shape, t.stride())
+        expect *= t.shape[d]
+    assert expect == inner, (what, expect, inner)
+    s = t.stride()[:3]
+    assert all(x >= 0 for x in s), (what, s)
+    room = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+    assert sum((t.shape[d] - 1) * s[d] for d in range(3)) + inner <= room, (what, "reaches outside its storage", t.shape, s, room)
+    return s
+
+
+GAT_TRACE_OUTPUTS = ("latent", "soft", "hard", "attn", "stats")
+
+
+def gat_trace(arena, src0, src1=None, hidden0=None, noise=None, tau=0.01, want=("latent",), weight=None, presence_col=-1, out=None,
+              lib=None):
+    """GAT_Net.forward walked over S consecutive steps in ONE launch (iplan_gat_trace), forward only: h_s = GAT([src0_s ||
+    src1_s], h_{s-1}), h_{-1} = hidden0 (None: zeros).  src0 [n_nets,B,S,N,d0], src1 [n_nets,B,S,N,d1] or None: views whose first
+    three dims may be strided arbitrarily (episode fields, read in place).  hidden0 [n_nets,B,N,A] (first two dims strided),
+    noise [n_nets,B,S,N,N-1,2] contiguous or None (no gumbel term), weight [n_nets,B,S] contiguous or None, ``presence_col``: the
+    column of src0 that marks a present entity (< 0: all).  ``want``: which of latent [n_nets,B,S,N,A], soft / hard / attn
+    [n_nets,B,S,N,N] (entity-indexed, diagonal 0), stats [n_nets,B,S,6] to produce; ``out``: optional dict of destination views for
+    some of them (the same layouts, first three dims strided).  Everything the kernel will touch is bounds-checked here, on
+    the host.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res = gat_trace_args(arena, src0, src1, hidden0, noise, tau, want, weight, presence_col, out)
+    n_nets, B, S, N, d0 = src0.shape
+    d1 = 0 if src1 is None else src1.shape[-1]
+    _launch("gat_trace_kernel", lambda: lib.call("iplan_gat_trace", a, L.current_stream(src0.device)), work=S * _gat_flops(n_nets, B, N, d0 + d1, 32))
+    return res
+
+
+def gat_trace_args(arena, src0, src1=None, hidden0=None, noise=None, tau=0.01, want=("latent",), weight=None, presence_col=-1, out=None):
+    """The descriptor of a ``gat_trace`` launch and its output tensors, checked but not launched: (IplanGatTraceArgs, dict).  The
+    caller keeps the operands alive until the launch has been queued."""
+    n_nets, B, S, N, d0 = src0.shape
+    d1 = 0 if src1 is None else src1.shape[-1]
+    A = 32
+    dev = src0.device
+    want = tuple(want)
+    assert want and all(k in GAT_TRACE_OUTPUTS for k in want), want
+    a = L.GatTraceArgs()
+    a.n_nets, a.B, a.N, a.d0, a.d1, a.S = n_nets, B, N, d0, d1, S
+    a.src0 = src0.data_ptr()
+    a.src0_s_net, a.src0_s_b, a.src0_s_step = _nbs_strides(src0, N * d0, "src0")
+    if src1 is not None:
+        assert src1.shape[:4] == (n_nets, B, S, N) and src1.device == dev, src1.shape
+        a.src1 = src1.data_ptr()
+        a.src1_s_net, a.src1_s_b, a.src1_s_step = _nbs_strides(src1, N * d1, "src1")
+    if hidden0 is not None:
+        assert hidden0.shape == (n_nets, B, N, A) and hidden0.device == dev, hidden0.shape
+        a.hidden0 = hidden0.data_ptr()
+        a.h_s_net, a.h_s_b, _ = _nbs_strides(hidden0.unsqueeze(2), N * A, "hidden0")
+    if noise is not None:
+        assert noise.is_contiguous() and noise.shape == (n_nets, B, S, N, N - 1, 2) and noise.dtype == torch.float32 and noise.device == dev, noise.shape
+        a.noise = noise.data_ptr()
+    if weight is not None:
+        assert weight.is_contiguous() and weight.shape == (n_nets, B, S) and weight.dtype == torch.float32 and weight.device == dev, weight.shape
+        a.weight = weight.data_ptr()
+    assert presence_col < d0
+    a.presence_col = max(int(presence_col), -1)
+    a.params = arena.data.data_ptr()
+    a.params_s_net = arena.net_stride
+    for i, k in enumerate(L.GAT_PARAM_ORDER):
+        a.off[i] = arena.off(k)
+    a.tau = tau
+    res = {}
+    for k in want:
+        inner = {"latent": (N, A), "stats": (L.GAT_TRACE_NSTAT,)}.get(k, (N, N))
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(n_nets, B, S, *inner, dtype=torch.float32, device=dev)
+        assert t.shape == (n_nets, B, S) + inner and t.device == dev, (k, t.shape)
+        n_in = inner[0] * (inner[1] if len(inner) > 1 else 1)
+        s = _nbs_strides(t, n_in, k)
+        setattr(a, k, t.data_ptr())
+        if k == "stats":
+            assert t.is_contiguous()
+        else:
+            pre = "lat" if k == "latent" else k
+            for name, v in zip(("net", "b", "step"), s):
+                setattr(a, f"{pre}_s_{name}", v)
+        res[k] = t
+    return a, res
+
+
 _FUSED_SYNC = {}
 
 
