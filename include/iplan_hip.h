@@ -854,6 +854,65 @@ typedef struct {
 int iplan_gat_trace(const IplanGatTraceArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Policy inspection: R_Actor / R_Critic (the comment above IplanAcNet) walked over S >= 1 consecutive steps of E >= 1 recorded
+ * chains in one call, forward only, with the GRU state carried by the nets under inspection:
+ *   h_s = GRU(trunk(x_s), h_{s-1}),   s = 0 .. S-1,   h_{-1} = hidden0 (NULL: zeros),   results of step s from LN(h_s) -> head.
+ * Row r = e*S + s (chain e, step s) is described by `feat` exactly as for iplan_ac_fwd (feat.T must equal S, so the row sits at
+ * physical row e*T_phys + s); its last action comes from feat.last_action / last_action64 (-1: all zeros), i.e. it is teacher-forced
+ * from the batch, so everything in front of the recurrent matrix is row-parallel.  One call enqueues two kernels on the stream:
+ *   phase 1 (trunk)  every net, every row: LN(F) (two passes), fc1 on v_mfma_f32_16x16x4_f32, act, LN, fc2, act, LN and
+ *                    gi = W_ih x + b_ih -> `gi`, a caller-provided workspace [2 (actor | critic), n_agents, E*S, IPLAN_AC_TRACE_GI];
+ *   phase 2 (walk)   one workgroup per 16-chain tile of one net steps s = 0 .. S-1 with W_hh in registers: W_hh h + b_hh, the gates,
+ *                    LN, head, masked softmax.
+ * which: 0 = actors, 1 = critics, 2 = both.  hidden0_*: rows of 64 floats at hidden0 + net*h0_s_net + e*h0_s_chain.  avail and
+ * actions_in are addressed by physical row as in IplanAcFwdArgs (avail NULL = all available).  packed_*: optional fc1 operands as
+ * iplan_ac_pack_fc1 leaves them (parts 0 or 1 suffice), NULL = read the arena in place; both give the same bits.
+ * Outputs, each optional (NULL = skip) and contiguous [n_agents, E, S, ...]:
+ *   probs   [.., n_actions]  unavailable actions exactly 0 (the masking of iplan_ac_fwd)
+ *   entropy, logp            as iplan_ac_fwd's entropy / logp of actions_in (mode 2); logp needs actions_in
+ *   greedy  int64            argmax of the row's own probs, lowest index on ties (mode 0 of iplan_ac_fwd)
+ *   values                   critic head
+ *   h_all_actor, h_all_critic  [.., 64]  the state after every step
+ * and always h_last_actor / h_last_critic [n_agents, E, 64] (of the nets `which` selects): the state after step S-1, which a
+ * following call takes as hidden0 -- a walk split into several calls gives the bits of the single call.
+ * fp32 throughout, fixed reduction order, no atomics: a row's results do not depend on the lane or tile its chain falls in, on how
+ * many chains share the tile, or on the split into calls.  1 <= n_actions <= 16, N <= IPLAN_MAX_ENTITIES; gi, the state outputs
+ * and the packed operands 16-byte aligned.  phases: 0 = both kernels; 1 = phase 1 only, 2 = phase 2 only (gi as a previous call
+ * left it) -- a timing aid for the phase split, nothing else uses it.
+ */
+#define IPLAN_AC_TRACE_GI (3 * IPLAN_AC_HIDDEN)
+typedef struct {
+    int32_t n_agents, E, S;
+    int32_t which;
+    int32_t act_tanh;           /* MLPBase activation: 0 = ReLU, 1 = tanh                                  */
+    int32_t phases;
+    IplanAcFeatures feat;
+    IplanAcNet actor, critic;
+    const float* hidden0_actor;
+    const float* hidden0_critic;
+    int64_t h0_s_net, h0_s_chain;
+    const int32_t* avail;
+    int64_t av_s_net, av_s_row;
+    const int64_t* actions_in;
+    int64_t act_s_net, act_s_row;
+    const float* packed_actor;
+    const float* packed_critic;
+    int64_t packed_s_net;
+    float* gi;
+    float* probs;
+    float* entropy;
+    int64_t* greedy;
+    float* logp;
+    float* values;
+    float* h_all_actor;
+    float* h_all_critic;
+    float* h_last_actor;
+    float* h_last_critic;
+} IplanAcTraceArgs;
+
+int iplan_ac_trace(const IplanAcTraceArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Three-layer perceptron of the FC behaviour ablation (nova/behavior_FC_net.py:6-37, Encoder_3FC / Decoder_3FC):
  *   out = [softmax] (W3 tanh(W2 tanh(W1 x + b1) + b2) + b3)   for n_nets stacked nets, rows per net.
  * off[0..5] = linear_1.weight [H,K0], linear_1.bias, linear_2.weight [H,H], linear_2.bias, out.weight [O,H], out.bias.

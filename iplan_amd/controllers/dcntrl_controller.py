@@ -12,6 +12,7 @@ Same constructor and method contracts as the reference.  Differences are interna
 """
 import copy
 
+import numpy as np
 import torch as th
 
 from .. import ops
@@ -122,6 +123,119 @@ class DcntrlMAC:
             return (values.cpu().numpy(), actions.cpu().numpy(), logps,
                     ha_new.cpu().numpy(), hc_new.cpu().numpy())
         return values, actions, logps, ha_new, hc_new
+
+    # ------------------------------------------------------------------------------ inspection
+    POLICY_STATS = ("weight", "entropy", "greedy_is_recorded", "logp", "value", "max_prob")
+
+    def _trace(self, batch, t0, S, hidden0, which, want, want_h):
+        """ops.policy_trace over steps t0 .. t0 + S - 1 of ``batch``, fields read in place -> ([nA, E, S, ..] results, as_numpy)"""
+        a = self.args
+        if a.layer_N != 1 or a.recurrent_N != 1:
+            raise NotImplementedError("policy_trace / action_distribution cover layer_N = recurrent_N = 1 only")
+        nA, N, M = self.n_agents, a.max_vehicle_num, a.rnn_hidden_dim
+        as_np = isinstance(batch["history"], np.ndarray)
+
+        def field(key, dtype=None):
+            """[E, T1, ...] on the device, rows addressable as e * T1 + t (a copy only when the batch's layout is not that)"""
+            t = batch[key]
+            t = self._dev(th.as_tensor(t) if isinstance(t, np.ndarray) else t, dtype)
+            return t if t.stride(0) == t.shape[1] * t.stride(1) and t[0, 0].is_contiguous() else t.contiguous()
+
+        hist = field("history", th.float32)
+        E, T1 = hist.shape[:2]
+        assert 0 <= t0 and t0 + S <= T1 and S >= 1, (t0, S, T1)
+        sources = []
+        for key, w in self._widths():
+            view = (hist if key == "history" else field(key, th.float32))[:, t0:t0 + S]          # [E, S, nA, N, w]
+            sources.append((view, w, view.stride(2), view.stride(1)))
+        acts = field("actions")[..., 0]                                                       # [E, T1, nA] int64
+        last, la_strides = None, (0, 0)
+        if a.obs_last_action:
+            last = th.cat([th.full_like(acts[:, :1], -1), acts[:, :-1]], 1)[:, t0:t0 + S]     # the action of t - 1; none at t = 0
+            la_strides = (last.stride(2), last.stride(1))
+        spec = ops.AcFeatureSpec(N, sources, n_actions=a.n_actions if a.obs_last_action else 0, last_action=last, la_strides=la_strides,
+                                 n_id=nA if a.obs_agent_id else 0, T=S, T_phys=T1)
+        assert spec.F == self.input_shape, (spec.F, self.input_shape)
+        avail = field("avail_actions")
+        if avail.dtype != th.int32:
+            avail = avail.to(th.int32)
+        avail = avail[:, t0:t0 + S]
+        acts = acts[:, t0:t0 + S]
+        if isinstance(hidden0, str):
+            assert hidden0 == "zeros", hidden0
+            ha = hc = None
+            hs = (0, 0)
+        else:
+            if hidden0 is None:
+                ha, hc = field("rnn_states_actors", th.float32)[:, t0], field("rnn_states_critics", th.float32)[:, t0]
+            else:
+                ha, hc = (self._dev(th.as_tensor(h), th.float32) for h in hidden0)
+            assert ha.shape == hc.shape == (E, nA, M), (ha.shape, hc.shape)
+            if ha.stride() != hc.stride() or ha.stride(2) != 1:
+                ha, hc = ha.contiguous(), hc.contiguous()
+            hs = (ha.stride(1), ha.stride(0))
+        w = {"actor": 0, "critic": 1, "both": 2}[which]
+        want = tuple(k for k in want if (k == "values" and w != 0) or (k != "values" and w != 1))
+        if want_h:
+            want += tuple(k for k, on in (("h_actor", w != 1), ("h_critic", w != 0)) if on)
+        res = ops.policy_trace(self.actor_arena, self.critic_arena, w, spec, E, S, nA, hidden0_actor=ha, hidden0_critic=hc, h_strides=hs,
+                               avail=avail, avail_strides=(avail.stride(2), avail.stride(1)),
+                               actions_in=acts if "logp" in want else None, act_strides=(acts.stride(2), acts.stride(1)),
+                               n_actions=a.n_actions, want=want, packed=self.fc1_pack.get(spec))
+        return res, as_np, acts
+
+    def policy_trace(self, batch, hidden0=None, which="both", want=("probs", "entropy", "greedy", "logp", "values", "stats"), return_hidden=False):
+        """What would these actors and critics have done on a recorded episode batch, step by step?  ``batch``: what
+        ``IPPOLearner.insert_episode_batch`` takes (fields [E, S, nA, ...], torch or numpy).  The nets walk the S steps with THEIR
+        OWN GRU state, carried inside one pair of launches (ops.policy_trace); step s sees what the rollout showed the policy at
+        t_ep = s: history / attention_latent / behavior_latent of step s (as GAT_enable / Behavior_enable say), the one-hot of the
+        recorded ``actions[:, s-1]`` (zeros at s = 0; obs_last_action), the agent id (obs_agent_id) and ``avail_actions[:, s]``.
+        ``hidden0``: None = the batch's ``rnn_states_actors[:, 0]`` / ``rnn_states_critics[:, 0]``, "zeros", or a pair of
+        [E, nA, M] tensors.  ``which``: "actor", "critic" or "both".  Returns a dict with those of ``want`` the nets provide:
+          probs [E,S,nA,n_actions] (unavailable actions exactly 0); entropy, logp (of the recorded ``actions[:, s]``), values
+          [E,S,nA]; greedy [E,S,nA] int64 (argmax of probs, lowest index on ties);
+          h_actor / h_critic [E,nA,M], the state after the last step -- [E,S,nA,M], after every step, with ``return_hidden``;
+          stats [nA,S,6] float64 (which = "both" only): sums over the environments with weight ``batch["filled"][:, s]`` of
+          POLICY_STATS = (the weight, entropy, 1[greedy == recorded action], logp, value, largest probability), formed on the
+          device in float64 from the per-row outputs, in environment order.
+        Device tensors in -> device tensors out, numpy in -> numpy out.  Draws from no generator; parameters, optimiser state,
+        ``hidden_states`` and the batch are not touched.  Not covered: a free-running replay that feeds the policy's own greedy
+        action back as the last action (the last action is always the recorded one), GAE / explained variance on the traced
+        values, and layer_N / recurrent_N other than 1."""
+        want = tuple(want)
+        known = ("probs", "entropy", "greedy", "logp", "values", "stats")
+        assert all(k in known for k in want), want
+        stats = "stats" in want
+        if stats and which != "both":
+            raise ValueError('policy_trace: "stats" needs which="both" (its columns come from the actors and the critics)')
+        S = batch["history"].shape[1]
+        need = known[:5] if stats else tuple(k for k in want if k != "stats")
+        res, as_np, acts = self._trace(batch, 0, S, hidden0, which, need, return_hidden)
+        out = {}
+        for k in want:
+            if k in res:
+                out[k] = res[k].permute(1, 2, 0, 3) if k == "probs" else res[k].permute(1, 2, 0)
+        for k in ("h_actor", "h_critic"):
+            if "h_last_" + k[2:] in res:
+                out[k] = res[k].permute(1, 2, 0, 3) if return_hidden else res["h_last_" + k[2:]].permute(1, 0, 2)
+        if stats:
+            filled = batch["filled"]
+            wt = self._dev(th.as_tensor(filled) if isinstance(filled, np.ndarray) else filled).reshape(-1, S).to(th.float64)     # [E, S]
+            cols = th.stack([th.ones_like(res["entropy"]), res["entropy"], (res["greedy"] == acts.permute(2, 0, 1)).to(th.float32), res["logp"],
+                             res["values"], res["probs"].max(-1).values], -1).to(th.float64)                                 # [nA, E, S, 6]
+            tot = th.zeros(self.n_agents, S, len(self.POLICY_STATS), dtype=th.float64, device=self.device)
+            for e in range(cols.shape[1]):                                        # environment order
+                tot += cols[:, e] * wt[e][None, :, None]
+            out["stats"] = tot
+        return {k: v.cpu().numpy() for k, v in out.items()} if as_np else out
+
+    def action_distribution(self, ep_batch, t_ep):
+        """The distribution ``select_actions_ippo(ep_batch, t_ep)`` samples from, which it never returns: one step of
+        ``policy_trace`` from the stored states ``rnn_states_*[:, t_ep]``.  Returns a dict: probs [E,nA,n_actions], greedy [E,nA]
+        int64, entropy [E,nA], values [E,nA] (device tensors in -> device tensors out, numpy in -> numpy out)."""
+        res, as_np, _ = self._trace(ep_batch, t_ep, 1, None, "both", ("probs", "greedy", "entropy", "values"), False)
+        out = {k: res[k][:, :, 0].transpose(0, 1) for k in ("probs", "greedy", "entropy", "values")}
+        return {k: v.cpu().numpy() for k, v in out.items()} if as_np else out
 
     def get_value_ippo(self, agent_id, obs, rnn_states_critic):
         """controllers/dcntrl_controller.py:61-68."""

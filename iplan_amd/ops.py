@@ -453,6 +453,120 @@ def ac_forward(actor_arena, critic_arena, which, spec, rows, n_agents, h_actor=N
     return out
 
 
+POLICY_TRACE_OUTPUTS = ("probs", "entropy", "greedy", "logp", "values", "h_actor", "h_critic")
+
+
+def _inside(t, reach, what):
+    """the last element a kernel can touch through ``t.data_ptr()``, ``reach`` elements past it, lies inside t's storage"""
+    room = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+    assert 0 <= reach <= room, (what, "reaches outside its storage", reach, room)
+
+
+def policy_trace(actor_arena, critic_arena, which, spec, E, S, n_agents, hidden0_actor=None, hidden0_critic=None, h_strides=(0, 0),
+                 avail=None, avail_strides=(0, 0), actions_in=None, act_strides=(0, 0), n_actions=5,
+                 want=("probs", "entropy", "greedy", "logp", "values"), packed=None, out=None, lib=None):
+    """R_Actor (which=0) / R_Critic (1) / both (2) of every agent walked over the S consecutive steps of E recorded chains
+    (iplan_ac_trace: a row-parallel trunk kernel, then a walk that carries the GRU state), forward only.  ``spec``: the rows'
+    features as for ``ac_forward`` with T = S -- row (e, s) at physical row e * T_phys + s, its last action teacher-forced from
+    ``spec.last_action`` (-1: zeros).  hidden0_* [.., 64] at net * h_strides[0] + e * h_strides[1] (None: zeros); avail int32 and
+    actions_in int64 are addressed by physical row with their (s_net, s_row) strides.  ``want``: which of probs [nA,E,S,n_actions],
+    entropy / logp / values [nA,E,S], greedy [nA,E,S] int64, h_actor / h_critic [nA,E,S,64] (the state after every step) to
+    produce; ``out``: optional dict of contiguous destinations for some of them.  The state after the last step is always
+    returned as h_last_actor / h_last_critic [nA,E,64].  ``packed``: Fc1Pack.get(spec) or None (same bits).  Everything the
+    kernels will read is bounds-checked here, on the host.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res, _keep = policy_trace_args(actor_arena, critic_arena, which, spec, E, S, n_agents, hidden0_actor, hidden0_critic, h_strides,
+                                      avail, avail_strides, actions_in, act_strides, n_actions, want, packed, out)
+    dev = (actor_arena if which != 1 else critic_arena).data.device
+    nets = n_agents * (2 if which == 2 else 1)
+    _launch("ac_trace", lambda: lib.call("iplan_ac_trace", a, L.current_stream(dev)),
+            work=2.0 * nets * E * S * L.AC_HIDDEN * (spec.F + 7 * L.AC_HIDDEN))
+    return res
+
+
+def policy_trace_args(actor_arena, critic_arena, which, spec, E, S, n_agents, hidden0_actor=None, hidden0_critic=None, h_strides=(0, 0),
+                      avail=None, avail_strides=(0, 0), actions_in=None, act_strides=(0, 0), n_actions=5,
+                      want=("probs", "entropy", "greedy", "logp", "values"), packed=None, out=None):
+    """The descriptor of a ``policy_trace`` launch, its output tensors and the operands to keep alive until the launch has been
+    queued, checked but not launched: (IplanAcTraceArgs, dict, tuple)."""
+    assert which in (0, 1, 2) and E >= 1 and S >= 1 and n_agents >= 1, (which, E, S, n_agents)
+    want = tuple(want)
+    assert all(k in POLICY_TRACE_OUTPUTS for k in want), want
+    arena0 = actor_arena if which != 1 else critic_arena
+    dev = arena0.data.device
+    M = L.AC_HIDDEN
+    a = L.AcTraceArgs()
+    a.n_agents, a.E, a.S, a.which = n_agents, E, S, which
+    a.act_tanh = int(bool(getattr(arena0, "act_tanh", False)))
+    if which == 2:
+        assert bool(getattr(actor_arena, "act_tanh", False)) == bool(getattr(critic_arena, "act_tanh", False)), \
+            "actor and critic of one trace must use the same trunk activation (args.use_ReLU)"
+    assert spec.T == S and spec.T_phys >= S, (spec.T, spec.T_phys, S)
+    spec.fill(a.feat)
+    last_row = (E - 1) * spec.T_phys + S - 1                         # the largest physical row
+    for t, w, s_net, s_row in spec.sources:
+        assert t.device == dev and min(s_net, s_row) >= 0
+        _inside(t, (n_agents - 1) * s_net + last_row * s_row + spec.N * w, "feature source")
+    if spec.last_action is not None and spec.n_actions > 0:
+        assert spec.last_action.device == dev and min(spec.la_strides) >= 0
+        _inside(spec.last_action, (n_agents - 1) * spec.la_strides[0] + last_row * spec.la_strides[1] + 1, "last_action")
+    f32 = dict(dtype=torch.float32, device=dev)
+    res = {}
+
+    def dest(k, shape, dtype=torch.float32):
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(*shape, dtype=dtype, device=dev)
+        assert t.shape == tuple(shape) and t.dtype == dtype and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
+        res[k] = t
+        return t.data_ptr()
+
+    for net, h0, key in ((0, hidden0_actor, "actor"), (1, hidden0_critic, "critic")):
+        if which == 1 - net:
+            continue
+        if h0 is not None:
+            assert h0.dtype == torch.float32 and h0.device == dev and min(h_strides) >= 0
+            _inside(h0, (n_agents - 1) * h_strides[0] + (E - 1) * h_strides[1] + M, "hidden0_" + key)
+            setattr(a, "hidden0_" + key, h0.data_ptr())
+        setattr(a, "h_last_" + key, dest("h_last_" + key, (n_agents, E, M)))
+        if "h_" + key in want:
+            setattr(a, "h_all_" + key, dest("h_" + key, (n_agents, E, S, M)))
+    a.h0_s_net, a.h0_s_chain = h_strides
+    if which != 1:
+        _fill_acnet(a.actor, actor_arena, L.ACTOR_PARAM_ORDER, n_actions)
+        if avail is not None:
+            assert avail.dtype == torch.int32 and avail.device == dev and min(avail_strides) >= 0
+            _inside(avail, (n_agents - 1) * avail_strides[0] + last_row * avail_strides[1] + n_actions, "avail")
+            a.avail = avail.data_ptr()
+            a.av_s_net, a.av_s_row = avail_strides
+        if actions_in is not None:
+            assert actions_in.dtype == torch.int64 and actions_in.device == dev and min(act_strides) >= 0
+            _inside(actions_in, (n_agents - 1) * act_strides[0] + last_row * act_strides[1] + 1, "actions_in")
+            a.actions_in = actions_in.data_ptr()
+            a.act_s_net, a.act_s_row = act_strides
+        if "probs" in want:
+            a.probs = dest("probs", (n_agents, E, S, n_actions))
+        if "entropy" in want:
+            a.entropy = dest("entropy", (n_agents, E, S))
+        if "greedy" in want:
+            a.greedy = dest("greedy", (n_agents, E, S), torch.int64)
+        if "logp" in want:
+            a.logp = dest("logp", (n_agents, E, S))
+    if which != 0:
+        _fill_acnet(a.critic, critic_arena, L.CRITIC_PARAM_ORDER, 1)
+        if "values" in want:
+            a.values = dest("values", (n_agents, E, S))
+    if packed is not None:                                 # Fc1Pack.get(spec): the fragment part is all the trunk reads
+        pa, pc = packed
+        if which != 1:
+            a.packed_actor, a.packed_s_net = pa.data_ptr(), pa.stride(0)
+        if which != 0:
+            a.packed_critic, a.packed_s_net = pc.data_ptr(), pc.stride(0)
+    gi = workspace(dev, 2 * n_agents * E * S * L.AC_TRACE_GI, "ac_trace")
+    a.gi = gi.data_ptr()
+    return a, res, (spec, hidden0_actor, hidden0_critic, avail, actions_in, packed, gi)
+
+
 def ac_xhat_pack(spec, rows, n_agents, ln_stats, lib=None):
     """The normalised feature rows of a PPO batch, gathered once per train() into the two fragment-major copies the
     split-bf16 fc1 kernels stream (include/iplan_hip.h: IplanAcXhatArgs).  ``ln_stats``: the (mean, rstd) table a

@@ -323,3 +323,83 @@ if "masked_wgrad" in set(sys.argv[1:]):
             loop.behavior._dec_stream.synchronize()
             ts.append((time.perf_counter() - t0) * 1e3)
         print(f"deferred decoder update on {k or 256} CUs: {min(ts[1:]):.2f} ms after learn() returned (host clock)")
+
+if "policy_trace" in set(sys.argv[1:]):
+    # policy inspection (iplan_ac_trace: row-parallel trunk + one walk, both nets of every agent) against the only way the same numbers could
+    # be had before it: S successive rollout-shaped ops.ac_forward(mode=2) launches of E rows with the state fed forward -- on the first S
+    # steps of a rollout's own batch, alternating in one process; then the trace's two phases on their own
+    S = int(os.environ.get("MB_TRACE_STEPS", "89"))
+    mac = loop.mac
+    D = batch.data
+    T1 = D["history"].shape[1]
+    n_act = args.n_actions
+    acts = D["actions"][..., 0]                                                            # [E, T1, nA]
+    last = torch.cat([torch.full_like(acts[:, :1], -1), acts[:, :-1]], 1)
+    avail = D["avail_actions"]
+    srcs = [(D[k][:, :S], w, D[k].stride(2), D[k].stride(1)) for k, w in mac._widths()]
+    spec = ops.AcFeatureSpec(N, srcs, n_actions=n_act, last_action=last[:, :S], la_strides=(last.stride(2), last.stride(1)), n_id=nA, T=S, T_phys=T1)
+    ha0, hc0 = D["rnn_states_actors"][:, 0], D["rnn_states_critics"][:, 0]
+    kw = dict(hidden0_actor=ha0, hidden0_critic=hc0, h_strides=(ha0.stride(1), ha0.stride(0)), avail=avail[:, :S], avail_strides=(avail.stride(2), avail.stride(1)),
+              actions_in=acts[:, :S], act_strides=(acts.stride(2), acts.stride(1)), n_actions=n_act)
+
+    def run_trace():
+        return ops.policy_trace(mac.actor_arena, mac.critic_arena, 2, spec, E, S, nA, packed=mac.fc1_pack.get(spec), **kw)
+
+    step_specs = []
+    for s in range(S):
+        views = [(D[k][:, s], w, D[k].stride(2), D[k].stride(0)) for k, w in mac._widths()]
+        la = last[:, s]
+        step_specs.append(ops.AcFeatureSpec(N, views, n_actions=n_act, last_action=la, la_strides=(la.stride(1), la.stride(0)), n_id=nA, T=E, T_phys=E))
+
+    def run_steps():
+        ha, hc, hs = ha0, hc0, (ha0.stride(1), ha0.stride(0))
+        outs = []
+        for s in range(S):
+            av, ac = avail[:, s], acts[:, s]
+            o = ops.ac_forward(mac.actor_arena, mac.critic_arena, 2, step_specs[s], E, nA, h_actor=ha, h_critic=hc, h_strides=hs, avail=av,
+                               avail_strides=(av.stride(1), av.stride(0)), mode=2, actions_in=ac, act_strides=(ac.stride(1), ac.stride(0)), n_actions=n_act,
+                               want_probs=True, want_entropy=True, packed=mac.fc1_pack.get(step_specs[s], fold=True))
+            ha, hc, hs = o["h_actor"], o["h_critic"], (E * 64, 64)
+            outs.append(o)
+        return outs
+
+    a_, b_ = run_trace(), run_steps()
+    torch.cuda.synchronize()
+    for k in ("values", "logp"):
+        ref = torch.stack([o[k] for o in b_], -1)
+        print(f"policy_trace vs {S} ac_forward steps, {k}: max |difference| {(a_[k] - ref).abs().max().item():.3g} (scale {ref.abs().max().item():.3g})", flush=True)
+    del a_, b_
+
+    def passes(fn, n_pass=5, n=3):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(n_pass):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) / n)
+        return out
+
+    lib = ops._lib(None)
+    targs, tres, tkeep = ops.policy_trace_args(mac.actor_arena, mac.critic_arena, 2, spec, E, S, nA, packed=mac.fc1_pack.get(spec), **kw)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def run_phase(p):
+        targs.phases = p
+        lib.call("iplan_ac_trace", targs, stream)
+
+    res = {"policy_trace": [], "ac_forward x S": [], "trace phase 1 (trunk)": [], "trace phase 2 (walk)": []}
+    for _ in range(2):                                     # the candidates alternate, so a drift of the box hits all of them
+        res["policy_trace"] += passes(run_trace)
+        res["ac_forward x S"] += passes(run_steps)
+        res["trace phase 1 (trunk)"] += passes(lambda: run_phase(1))
+        res["trace phase 2 (walk)"] += passes(lambda: run_phase(2))
+    for k, v in res.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        print(f"{k:24s} E={E} S={S} nA={nA} both nets: median {med:.4f} ms  min {v[0]:.4f}  max {v[-1]:.4f}  spread {(v[-1] - v[0]) / med * 100:.1f} %", flush=True)
