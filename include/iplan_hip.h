@@ -549,6 +549,65 @@ typedef struct {
 
 int iplan_ppo_loss(const IplanPpoLossArgs* args, iplan_stream_t stream);
 
+/* iplan_ppo_eval: how a recorded batch scores under the nets, forward only -- the five statistics of iplan_ppo_loss plus the
+ * numbers a PPO user reads first, per agent and per episode step, with no gradient and nothing stepped
+ * (IPPOLearner.evaluate).  Inputs are addressed exactly as in IplanPpoLossArgs: the first `rows` rows of every agent are
+ * scored, row r = b * T + t; `adv` is the RAW advantage iplan_ppo_prepare(skip_norm = 1) leaves and is normalised HERE as
+ * iplan_ppo_prepare normalises it: mean and unbiased std + 1e-5 over ALL row_stride entries of the agent (two passes).
+ * With m = mask, ratio = exp(logp - old_logp), sums over the first `rows` rows, S = sum m:
+ *   stats[net][ 0.. 4] policy_loss, value_loss, mean ratio, mean entropy, S        (iplan_ppo_loss's definitions, flags included;
+ *                                                                                   the value loss is NOT scaled by value_loss_coef)
+ *   stats[net][ 5]     approx_kl (k1)    = sum m (old_logp - logp) / S
+ *   stats[net][ 6]     approx_kl_k3      = sum m ((ratio - 1) - (logp - old_logp)) / S
+ *   stats[net][ 7]     clip_fraction     = sum m [|ratio - 1| > clip] / S
+ *   stats[net][ 8, 9]  largest and smallest ratio over the rows with m != 0
+ *   stats[net][10]     explained_variance = 1 - Var_m(returns - value_preds) / Var_m(returns), masked population variances taken
+ *                      in two passes (NaN or -inf when Var_m(returns) == 0, as the formula gives)
+ *   stats[net][11]     value_clip_fraction = sum m [|values - value_preds| > clip] / S
+ *   stats[net][12,13]  mean and unbiased std of the raw advantage over the row_stride entries: the normaliser's two numbers
+ *   stats[net][14]     sum m returns / S
+ *   stats[net][15]     sum m |returns - values| / S
+ *   step_stats[net][t][0..5], over the episodes b < rows / T in episode order: live count c = sum_b m, then sum_b m x / c for
+ *                      x = raw advantage, |returns - values|, ratio, entropy, [|ratio - 1| > clip]; exact zeros where c == 0.
+ * Reduction order (no atomics; every bit of every output is the same for any n_parts and from call to call): the row axis is
+ * cut into chunks of IPLAN_PPO_EVAL_CHUNK rows.  A chunk is reduced by one 256-thread workgroup -- a row per thread, fp32
+ * xor-butterfly per wave, the four waves added in wave order in fp64 -- into one fp64 partial per quantity in `workspace`;
+ * whoever needs a total adds the chunk partials in chunk order in fp64.  Four launches on the stream, a launch boundary
+ * between a phase that writes partials and the one that reads them:
+ *   1. per chunk: sum adv, S, sum m returns, sum m (returns - value_preds)
+ *   2. per chunk, around the means of 1: sum (adv - mean)^2, sum m (returns - mean)^2, sum m (residual - mean)^2
+ *   3. per chunk, with S and the advantage's mean / std of 1 and 2: the loss terms, KLs, fractions, extrema; ratio, adv_norm
+ *   4. one workgroup per agent adds up -> stats;  one thread per (agent, t) walks b = 0, 1, ... -> step_stats
+ * n_parts workgroups per agent take the chunks p, p + n_parts, ...: it changes who computes a chunk, never what is added. */
+#define IPLAN_PPO_EVAL_CHUNK 256     /* rows per chunk = threads per workgroup                                     */
+#define IPLAN_PPO_EVAL_STATS 16
+#define IPLAN_PPO_EVAL_STEP_STATS 6
+#define IPLAN_PPO_EVAL_WS 18         /* fp64 workspace slots per (agent, chunk)                                    */
+typedef struct {
+    int32_t n_agents, rows;
+    int64_t row_stride;          /* per-agent stride of the [n_agents, bs*T] inputs below; >= 2, >= rows, < 2^31   */
+    const float* logp;           /* [n_agents, rows] current log-probs (iplan_ac_fwd output)                       */
+    const float* entropy;        /* [n_agents, rows]                                                               */
+    const float* values;         /* [n_agents, rows] current values                                                */
+    const float* old_logp;       /* [n_agents, row_stride]                                                         */
+    const float* adv;            /* [n_agents, row_stride] RAW advantages, read over all row_stride entries        */
+    const float* value_preds;
+    const float* returns;
+    const float* mask;
+    float clip, huber_delta, value_loss_coef;   /* (value_loss_coef: carried with the other two; no statistic uses it) */
+    int32_t flags;               /* IPLAN_PPO_* bits                                                               */
+    int32_t T;                   /* steps per episode; rows must be a multiple of it                               */
+    int32_t n_parts;             /* workgroups per agent, 0 / 1 = one; clamped to the number of chunks and to 1024 */
+    float* stats;                /* [n_agents, IPLAN_PPO_EVAL_STATS]                                               */
+    float* step_stats;           /* [n_agents, T, IPLAN_PPO_EVAL_STEP_STATS]                                       */
+    float* ratio;                /* optional [n_agents, rows]                     (NULL = skip)                    */
+    float* adv_norm;             /* optional [n_agents, row_stride] normalised advantages; must not alias adv      */
+    void* workspace;             /* iplan_ppo_eval_workspace_bytes(n_agents, row_stride) bytes, 8-byte aligned; scratch */
+} IplanPpoEvalArgs;
+
+int64_t iplan_ppo_eval_workspace_bytes(int32_t n_agents, int64_t row_stride);
+int iplan_ppo_eval(const IplanPpoEvalArgs* args, iplan_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Backward of GAT_Net.forward (autograd under loss.backward() at nova/prediction_policy.py:228) for
  * every (net, env) scene in one launch: GRUCell', gated soft attention', gumbel gate', BPTT through

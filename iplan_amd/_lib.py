@@ -53,9 +53,10 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_pdec_fwd", "iplan_pdec_bwd", "iplan_beh_fwd", "iplan_beh_bwd", "iplan_mlp3_fwd", "iplan_mlp3_bwd", "iplan_seq2seq_fwd", "iplan_ac_pack_fc1",
                 "iplan_ac_xhat_pack", "iplan_ac_fc1_split_fwd", "iplan_ac_bwd_fc1_split",
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
-                "iplan_gat_trace", "iplan_ac_trace"]
+                "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
-                    "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts"]      # non (args*, stream) signatures
+                    "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
+                    "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
 
 
 class Lib:
@@ -88,6 +89,8 @@ class Lib:
         cdll.iplan_gat_enc_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         cdll.iplan_gat_enc_ac_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         cdll.iplan_gumbel_noise.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]
+        cdll.iplan_ppo_eval_workspace_bytes.restype = C.c_int64
+        cdll.iplan_ppo_eval_workspace_bytes.argtypes = [C.c_int32, C.c_int64]
         cdll.iplan_p2p_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
         cdll.iplan_p2p_free.argtypes = [C.c_void_p]
         cdll.iplan_p2p_export.argtypes = [C.c_void_p, C.POINTER(IpcHandle)]
@@ -312,6 +315,25 @@ class PpoLossArgs(C.Structure):
 PPO_MSE, PPO_NO_VCLIP, PPO_VALUE_MEAN, PPO_POLICY_MEAN = 1, 2, 4, 8
 
 
+class PpoEvalArgs(C.Structure):
+    _fields_ = [
+        ("n_agents", i32), ("rows", i32), ("row_stride", i64),
+        ("logp", fp), ("entropy", fp), ("values", fp), ("old_logp", fp), ("adv", fp),
+        ("value_preds", fp), ("returns", fp), ("mask", fp),
+        ("clip", C.c_float), ("huber_delta", C.c_float), ("value_loss_coef", C.c_float),
+        ("flags", i32), ("T", i32), ("n_parts", i32),
+        ("stats", fp), ("step_stats", fp), ("ratio", fp), ("adv_norm", fp), ("workspace", fp),
+    ]
+
+
+PPO_EVAL_CHUNK = 256             # IPLAN_PPO_EVAL_CHUNK
+# stats[net][k] of iplan_ppo_eval, in order, and the columns of step_stats[net][t]
+PPO_EVAL_STATS = ("policy_loss", "value_loss", "ratio_mean", "dist_entropy", "mask_sum", "approx_kl", "approx_kl_k3", "clip_fraction",
+                  "ratio_max", "ratio_min", "explained_variance", "value_clip_fraction", "adv_mean", "adv_std", "return_mean",
+                  "value_abs_error")
+PPO_EVAL_STEP_STATS = ("count", "adv_mean", "value_abs_error", "ratio", "entropy", "clip_fraction")
+
+
 # ---- GAT backward --------------------------------------------------------------------------------------
 GAT_NODE_DY = 640
 GAT_HARD_PART = 8 * 32 + 16
@@ -458,4 +480,4 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanPdecArgs": PdecArgs, "IplanBehArgs": BehArgs, "IplanMlp3Args": Mlp3Args, "IplanAdvNormArgs": AdvNormArgs, "IplanSeq2SeqArgs": Seq2SeqArgs, "IplanSeq2SeqBwdArgs": Seq2SeqBwdArgs, "IplanAcPackArgs": AcPackArgs,
                   "IplanIpcHandle": IpcHandle, "IplanP2pArgs": P2pArgs, "IplanAcXhatArgs": AcXhatArgs, "IplanAcFc1SplitArgs": AcFc1SplitArgs,
                   "IplanObsHistArgs": ObsHistArgs, "IplanPredictArgs": PredictArgs, "IplanBehEvalArgs": BehEvalArgs,
-                  "IplanGatTraceArgs": GatTraceArgs, "IplanAcTraceArgs": AcTraceArgs}
+                  "IplanGatTraceArgs": GatTraceArgs, "IplanAcTraceArgs": AcTraceArgs, "IplanPpoEvalArgs": PpoEvalArgs}

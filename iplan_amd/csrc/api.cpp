@@ -1,4 +1,4 @@
-// C-ABI bookkeeping: version + thread-local error string.
+// C-ABI bookkeeping: version + thread-local error string; the argument checks of iplan_ppo_eval (kernels: ppo_eval.hip).
 #include <cstring>
 
 #include "api_util.h"
@@ -8,6 +8,7 @@ char* error_buffer() {
     static thread_local char buf[512] = {0};
     return buf;
 }
+int ppo_eval_launch(const IplanPpoEvalArgs& a, hipStream_t stream);   // ppo_eval.hip
 }  // namespace iplan
 
 extern "C" const char* iplan_last_error(void) { return iplan::error_buffer(); }
@@ -19,7 +20,33 @@ extern "C" size_t iplan_sizeof(const char* name) {
     IPLAN_SZ(IplanGatSaved) IPLAN_SZ(IplanGatFwdArgs) IPLAN_SZ(IplanGatBwdArgs) IPLAN_SZ(IplanEncFwdArgs) IPLAN_SZ(IplanAcNet)
     IPLAN_SZ(IplanAcFeatures) IPLAN_SZ(IplanAcFwdArgs) IPLAN_SZ(IplanAcBwdArgs) IPLAN_SZ(IplanAdamArgs) IPLAN_SZ(IplanWgradProblem)
     IPLAN_SZ(IplanWgradArgs) IPLAN_SZ(IplanPpoPrepareArgs) IPLAN_SZ(IplanPpoLossArgs) IPLAN_SZ(IplanPdecArgs) IPLAN_SZ(IplanBehArgs) IPLAN_SZ(IplanMlp3Args) IPLAN_SZ(IplanAdvNormArgs) IPLAN_SZ(IplanSeq2SeqArgs) IPLAN_SZ(IplanAcPackArgs) IPLAN_SZ(IplanP2pArgs) IPLAN_SZ(IplanIpcHandle) IPLAN_SZ(IplanAcXhatArgs) IPLAN_SZ(IplanAcFc1SplitArgs) IPLAN_SZ(IplanObsHistArgs) IPLAN_SZ(IplanSeq2SeqBwdArgs)
-    IPLAN_SZ(IplanPredictArgs) IPLAN_SZ(IplanBehEvalArgs) IPLAN_SZ(IplanGatTraceArgs) IPLAN_SZ(IplanAcTraceArgs)
+    IPLAN_SZ(IplanPredictArgs) IPLAN_SZ(IplanBehEvalArgs) IPLAN_SZ(IplanGatTraceArgs) IPLAN_SZ(IplanAcTraceArgs) IPLAN_SZ(IplanPpoEvalArgs)
 #undef IPLAN_SZ
     return 0;
+}
+
+extern "C" int64_t iplan_ppo_eval_workspace_bytes(int32_t n_agents, int64_t row_stride) {
+    if (n_agents < 1 || row_stride < 1 || row_stride > 0x7fffffff) return 0;
+    const int64_t chunks = (row_stride + IPLAN_PPO_EVAL_CHUNK - 1) / IPLAN_PPO_EVAL_CHUNK;
+    return (int64_t)n_agents * chunks * IPLAN_PPO_EVAL_WS * (int64_t)sizeof(double);
+}
+
+extern "C" int iplan_ppo_eval(const IplanPpoEvalArgs* a, iplan_stream_t stream) {
+    using namespace iplan;
+    if (!a) return fail(IPLAN_EINVAL, "iplan_ppo_eval: null args");
+    if (a->n_agents < 1) return fail(IPLAN_EINVAL, "iplan_ppo_eval: n_agents=%d, at least one agent is needed", a->n_agents);
+    if (a->T < 1 || a->rows < 1) return fail(IPLAN_EINVAL, "iplan_ppo_eval: rows=%d and T=%d must be positive", a->rows, a->T);
+    if (a->rows % a->T) return fail(IPLAN_EINVAL, "iplan_ppo_eval: rows=%d is not a multiple of T=%d", a->rows, a->T);
+    if (a->row_stride < a->rows) return fail(IPLAN_EINVAL, "iplan_ppo_eval: rows=%d > row_stride=%lld", a->rows, (long long)a->row_stride);
+    if (a->row_stride < 2 || a->row_stride > 0x7fffffff)
+        return fail(IPLAN_EINVAL, "iplan_ppo_eval: row_stride=%lld outside [2, 2^31): the unbiased std needs two entries", (long long)a->row_stride);
+    if (!a->logp || !a->entropy || !a->values || !a->old_logp || !a->adv || !a->value_preds || !a->returns || !a->mask)
+        return fail(IPLAN_EINVAL, "iplan_ppo_eval: a per-row input is null");
+    if (!a->stats || !a->step_stats || !a->workspace) return fail(IPLAN_EINVAL, "iplan_ppo_eval: stats, step_stats or workspace is null");
+    if (a->n_parts < 0) return fail(IPLAN_EINVAL, "iplan_ppo_eval: n_parts=%d is negative", a->n_parts);
+    if (a->flags & ~(IPLAN_PPO_MSE | IPLAN_PPO_NO_VCLIP | IPLAN_PPO_VALUE_MEAN | IPLAN_PPO_POLICY_MEAN))
+        return fail(IPLAN_EINVAL, "iplan_ppo_eval: unknown flag bits in %d", a->flags);
+    if (a->adv_norm == a->adv) return fail(IPLAN_EINVAL, "iplan_ppo_eval: adv_norm must not alias adv");
+    if (((size_t)a->workspace) & 7) return fail(IPLAN_EALIGN, "iplan_ppo_eval: workspace must be 8-byte aligned");
+    return ppo_eval_launch(*a, (hipStream_t)stream);
 }

@@ -214,8 +214,9 @@ class IPPOLearner:
         self.store.insert(ep_batch, min(self.batch_size_run, ep_batch.batch_size))
 
     # ------------------------------------------------------------------------------------------ train
-    def _feature_spec(self, T, T_phys, last):
-        a, d = self.args, self.store.data
+    def _feature_spec(self, T, T_phys, last, d=None):
+        """``d``: the episode fields to read in place (default: the store's)"""
+        a, d = self.args, self.store.data if d is None else d
         srcs = []
         for key, w in self.mac._widths():
             t = d[key]                                     # [bs, T1, nA, N, w]
@@ -224,14 +225,14 @@ class IPPOLearner:
                                  last_action=last, la_strides=(1, self.n_agents),
                                  n_id=self.n_agents if a.obs_agent_id else 0, T=T, T_phys=T_phys)
 
-    def _last_action_index(self):
+    def _last_action_index(self, d=None):
         """Hot index of the last-action block of every stored step ([bs, T1, nA] int32, -1 = an all-zero block): the
         reference feeds ``actions_onehot`` shifted by one step, ``actions_onehot[0]`` at t = 0
         (dcntrl_controller.py:105-108).  Steps a rollout never wrote (the runner breaks once every env has terminated,
         ippo_parallel_runner.py:212-214) keep ``actions`` = 0 but an all-zero ``actions_onehot`` row -- the OneHot
         preprocess only runs on updated slices -- so the index comes from the stored one-hot rows, not from ``actions``.
-        Index bookkeeping only (the rows are exact one-hots or zeros)."""
-        d = self.store.data
+        Index bookkeeping only (the rows are exact one-hots or zeros).  ``d``: the episode fields (default: the store's)."""
+        d = self.store.data if d is None else d
         oh = d.get("actions_onehot")
         if oh is None:
             idx = d["actions"][..., 0]
@@ -412,6 +413,149 @@ class IPPOLearner:
                     self.logger.log_stat(self.log_prefix + k, v, t_env)
             return train_info
         return finish if defer else (finish() and None)
+
+    # ------------------------------------------------------------------------------------------ evaluate
+    EVAL_ROW_TENSORS = ("values", "returns", "advantages", "advantages_raw", "logp", "ratio", "mask")
+
+    def _eval_fields(self, batch, episodes):
+        """The episode fields ``evaluate`` reads, [E, T1, nA, ...] on the learner's device with rows addressable as e * T1 + t (views
+        of the store or of the batch wherever their layout is that already) -> (dict, E, per-row results as numpy?)"""
+        keys = [k for k, _ in self.mac._widths()] + ["actions", "actions_onehot", "avail_actions", "reward", "terminated",
+                                                     "rnn_states_actors", "rnn_states_critics"]
+        if batch is None:
+            E = self.store.count if episodes is None else min(int(episodes), self.store.count)
+            if E < 1:
+                raise ValueError("evaluate: the store holds no episode")
+            return {k: self.store.data[k][:E] for k in keys if k in self.store.data}, E, False
+        import numpy as np
+        float_keys = {k for k, _ in self.mac._widths()} | {"reward", "rnn_states_actors", "rnn_states_critics", "actions_onehot"}
+        d, as_np = {}, None
+        for k in keys:
+            try:
+                t = batch[k]
+            except (KeyError, ValueError):
+                if k == "actions_onehot":
+                    continue
+                raise
+            host = isinstance(t, np.ndarray)
+            t = th.as_tensor(t)
+            if as_np is None:
+                as_np = host or (t.device.type == "cpu" and self.device.type != "cpu")
+            t = self.mac._dev(t, th.float32 if k in float_keys else None)
+            if episodes is not None:
+                t = t[:int(episodes)]
+            if k == "terminated" and t.dtype != th.uint8:
+                t = t.to(th.uint8)
+            if not (t.stride(0) == t.shape[1] * t.stride(1) and t[0, 0].is_contiguous()):
+                t = t.contiguous()
+            d[k] = t
+        E = d["history"].shape[0]
+        if E < 1:
+            raise ValueError("evaluate: the batch holds no episode")
+        return d, E, as_np
+
+    def evaluate(self, batch=None, old=None, old_logp=None, want=(), episodes=None):
+        """How does a recorded batch score under these nets?  Forward only: the launches of ``train()`` up to its first loss launch
+        -- the critics on all E (T + 1) stored rows with the stored critic states, iplan_ppo_prepare (raw advantages), the actors
+        and critics on the E T rows with the stored states -- then ONE iplan_ppo_eval launch sequence and ONE host read-back.  No
+        backward, no optimiser, no ``randperm``; all E T rows are scored at once whatever ``num_mini_batch`` says.
+
+        ``batch``: None = the store's current ``count`` episodes (it need not be full and is not cleared), else an EpisodeBatch
+        or dict with the fields ``train()`` reads ([E, T + 1, nA, ...], torch or numpy, host or device), read in place where their
+        layout allows.  ``episodes``: only the first k of them.
+        Where the "old" quantities come from:
+          * default: the old log-probs are the current actors' own -- ratio == 1, both KLs == 0 and the clip fraction == 0 exactly,
+            the losses are those of ``train()``'s first epoch;
+          * ``old`` = another DcntrlMAC of the same shapes (a snapshot): ITS critics give values / returns / advantages /
+            value_preds and ITS actors the old log-probs, this learner's nets give logp / values / entropy -- the loss a later PPO
+            epoch sees, and how far the nets have moved from the snapshot;
+          * ``old_logp`` [E, T, nA]: overrides the old log-probs only.  ``old`` and ``old_logp`` together raise ValueError.
+        Returns a dict: one float array [nA] per name of ``_lib.PPO_EVAL_STATS`` (policy_loss, value_loss, ratio_mean, dist_entropy,
+        mask_sum, approx_kl, approx_kl_k3, clip_fraction, ratio_max, ratio_min, explained_variance, value_clip_fraction, adv_mean,
+        adv_std, return_mean, value_abs_error; the advantage pair is the normaliser's mean / unbiased std of the raw advantage),
+        ``per_step`` [nA, T, 6] (``_lib.PPO_EVAL_STEP_STATS``: live count, then masked means over the episodes of the raw advantage,
+        |returns - values|, ratio, entropy and the clip indicator; zeros at a step nobody lived to), and for the names in ``want``
+        the per-row tensors values [E, T + 1, nA] (the critic pass the returns were built from) and returns / advantages
+        (normalised) / advantages_raw / logp / ratio / mask [E, T, nA] -- numpy if the batch was on the host, device tensors if it was
+        on the device.  Draws from no generator; parameters, gradients, Adam state, the store, ``mac.hidden_states``,
+        ``last_train_info`` and the batch are left as they are.  Data-parallel learners: not covered (NotImplementedError)."""
+        if self.dp is not None:
+            raise NotImplementedError("evaluate: statistics over the rows of all data-parallel ranks are not implemented")
+        if old is not None and old_logp is not None:
+            raise ValueError("evaluate: give `old` (a snapshot's nets) or `old_logp`, not both")
+        want = tuple(want)
+        unknown = [k for k in want if k not in self.EVAL_ROW_TENSORS]
+        if unknown:
+            raise ValueError(f"evaluate: unknown per-row tensors {unknown}; known: {self.EVAL_ROW_TENSORS}")
+        d, E, as_np = self._eval_fields(batch, episodes)
+        a, nA, mac = self.args, self.n_agents, self.mac
+        src = mac if old is None else old
+        T1 = d["history"].shape[1]
+        T = T1 - 1
+        if T < 1 or E * T < 2:
+            raise ValueError(f"evaluate: {E} episode(s) of {T} step(s) are too few for the advantage's unbiased std")
+        rows = E * T
+        dev = self.device
+        f32 = dict(dtype=th.float32, device=dev)
+        last = self._last_action_index(d)
+        ha, hc = d["rnn_states_actors"], d["rnn_states_critics"]
+        if ha.stride() != hc.stride():
+            ha, hc = ha.contiguous(), hc.contiguous()
+        hs = (ha.stride(2), ha.stride(1))
+        avail = d["avail_actions"]
+        if avail.dtype != th.int32:
+            avail = avail.to(th.int32)
+        actions = d["actions"]
+        if actions.dtype != th.int64:
+            actions = actions.to(th.int64)
+
+        # compute_returns (:344-365) with the critics of `src`; the advantages stay raw (the eval kernel normalises them)
+        spec_all = self._feature_spec(T1, T1, last, d)
+        ln_stats = th.empty(nA, E * T1, 2, **f32)
+        v_all = ops.ac_forward(None, src.critic_arena, 1, spec_all, E * T1, nA, h_critic=hc, h_strides=hs, ksplit=1, want_h=False,
+                               ln_stats=ln_stats, ln_stats_mode=1, packed=src.fc1_pack.get(spec_all))["values"]
+        rw, tm = d["reward"], d["terminated"]
+        pp = L.PpoPrepareArgs()
+        pp.n_agents, pp.bs, pp.T = nA, E, T
+        pp.reward, pp.rw_s_net, pp.rw_s_ep, pp.rw_s_t = rw.data_ptr(), rw.stride(2), rw.stride(0), rw.stride(1)
+        assert tm.dtype == th.uint8
+        pp.terminated, pp.tm_s_net, pp.tm_s_ep, pp.tm_s_t = tm.data_ptr(), tm.stride(2), tm.stride(0), tm.stride(1)
+        pp.values, pp.gamma, pp.lam = v_all.data_ptr(), self.gamma, self.gae_lambda
+        returns, adv, mask, vpred = (th.empty(nA, rows, **f32) for _ in range(4))
+        pp.returns, pp.adv, pp.mask, pp.value_preds = returns.data_ptr(), adv.data_ptr(), mask.data_ptr(), vpred.data_ptr()
+        pp.skip_norm = 1
+        pp.no_gae = 0 if self._use_gae else 1
+        L.get_lib().call("iplan_ppo_prepare", pp, L.current_stream(dev))
+
+        # this learner's nets on the E T rows, from the stored states (the fp32 contraction, which reads the fields in place)
+        spec = self._feature_spec(T, T1, last, d)
+        fwd_kw = dict(h_actor=ha, h_critic=hc, h_strides=hs, avail=avail, avail_strides=(avail.stride(2), avail.stride(1)), mode=2,
+                      actions_in=actions, act_strides=(actions.stride(2), actions.stride(1)), n_actions=a.n_actions, ksplit=1,
+                      want_h=False, ln_stats=ln_stats, ln_stats_mode=2)
+        out = ops.ac_forward(mac.actor_arena, mac.critic_arena, 2, spec, rows, nA, want_entropy=True, packed=mac.fc1_pack.get(spec), **fwd_kw)
+        if old is not None:
+            olp = ops.ac_forward(old.actor_arena, None, 0, spec, rows, nA, packed=old.fc1_pack.get(spec), **fwd_kw)["logp"]
+        elif old_logp is not None:
+            olp = mac._dev(th.as_tensor(old_logp), th.float32)
+            if olp.dim() != 3 or olp.shape[0] < E or tuple(olp.shape[1:]) != (T, nA):
+                raise ValueError(f"evaluate: old_logp must be [E >= {E}, {T}, {nA}], got {tuple(olp.shape)}")
+            olp = olp[:E].permute(2, 0, 1).reshape(nA, rows).contiguous()
+        else:
+            olp = out["logp"]
+        kwant = tuple(k for k, name in (("ratio", "ratio"), ("adv_norm", "advantages")) if name in want)
+        res = ops.ppo_eval(out["logp"], out["entropy"], out["values"], olp, adv, vpred, returns, mask, T, clip=self.clip_param,
+                           huber_delta=self.huber_delta, value_loss_coef=self.value_loss_coef, flags=self._loss_flags,
+                           n_parts=min(64, rows // 1024), want=kwant)
+        n_st = res["stats"].numel()
+        host = th.cat([res["stats"].reshape(-1), res["step_stats"].reshape(-1)]).cpu()          # the one read-back
+        stats = host[:n_st].reshape(nA, -1).numpy()
+        result = {name: stats[:, k].copy() for k, name in enumerate(L.PPO_EVAL_STATS)}
+        result["per_step"] = host[n_st:].reshape(nA, T, -1).numpy()
+        rows_of = dict(returns=returns, advantages=res.get("adv_norm"), advantages_raw=adv, logp=out["logp"], ratio=res.get("ratio"), mask=mask)
+        for k in want:
+            t = v_all.reshape(nA, E, T1).permute(1, 2, 0) if k == "values" else rows_of[k].reshape(nA, E, T).permute(1, 2, 0)
+            result[k] = t.cpu().numpy() if as_np else t
+        return result
 
     def _train_minibatches(self, t_env, rows, last, ln_stats, old_logp, adv, returns, vpred, mask):
         """num_mini_batch > 1 (generate_data, learners/ippo_learner.py:368-424): every epoch draws a fresh ``randperm`` of the

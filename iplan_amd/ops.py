@@ -567,6 +567,61 @@ def policy_trace_args(actor_arena, critic_arena, which, spec, E, S, n_agents, hi
     return a, res, (spec, hidden0_actor, hidden0_critic, avail, actions_in, packed, gi)
 
 
+def ppo_eval(logp, entropy, values, old_logp, adv, value_preds, returns, mask, T, rows=None, clip=0.2, huber_delta=10.0,
+             value_loss_coef=1.0, flags=0, n_parts=0, want=(), out=None, lib=None):
+    """The PPO statistics of recorded rows under the nets, forward only (iplan_ppo_eval; include/iplan_hip.h: IplanPpoEvalArgs).
+    logp / entropy / values [nA, rows]; old_logp / adv (RAW, normalised in the kernel over all row_stride entries) / value_preds /
+    returns / mask [nA, row_stride], row r = b * T + t; ``rows`` defaults to logp's.  ``want``: which of the per-row outputs "ratio"
+    [nA, rows] and "adv_norm" [nA, row_stride] to produce; ``out``: optional dict of contiguous destinations.  ``n_parts``:
+    workgroups per agent -- any value gives the same bits.  Returns a dict: stats [nA, 16] (_lib.PPO_EVAL_STATS), step_stats
+    [nA, T, 6] (_lib.PPO_EVAL_STEP_STATS) and the wanted per-row tensors."""
+    lib = _lib(lib)
+    a, res, _keep = ppo_eval_args(logp, entropy, values, old_logp, adv, value_preds, returns, mask, T, rows, clip, huber_delta,
+                                  value_loss_coef, flags, n_parts, want, out, lib)
+    _launch("ppo_eval", lambda: lib.call("iplan_ppo_eval", a, L.current_stream(logp.device)))
+    return res
+
+
+def ppo_eval_args(logp, entropy, values, old_logp, adv, value_preds, returns, mask, T, rows=None, clip=0.2, huber_delta=10.0,
+                  value_loss_coef=1.0, flags=0, n_parts=0, want=(), out=None, lib=None):
+    """The descriptor of a ``ppo_eval`` launch, its output tensors and the operands to keep alive until the launch has been
+    queued, checked but not launched: (IplanPpoEvalArgs, dict, tuple)."""
+    lib = _lib(lib)
+    want = tuple(want)
+    assert all(k in ("ratio", "adv_norm") for k in want), want
+    dev = logp.device
+    nA = logp.shape[0]
+    rows = logp.shape[1] if rows is None else rows
+    stride = old_logp.shape[1]
+    for name, t, width in (("logp", logp, rows), ("entropy", entropy, rows), ("values", values, rows), ("old_logp", old_logp, stride),
+                           ("adv", adv, stride), ("value_preds", value_preds, stride), ("returns", returns, stride), ("mask", mask, stride)):
+        assert t.dtype == torch.float32 and t.device == dev and t.shape == (nA, width) and t.is_contiguous(), (name, t.shape, t.dtype, width)
+    a = L.PpoEvalArgs()
+    a.n_agents, a.rows, a.row_stride, a.T, a.n_parts = nA, rows, stride, T, n_parts
+    a.logp, a.entropy, a.values, a.old_logp = logp.data_ptr(), entropy.data_ptr(), values.data_ptr(), old_logp.data_ptr()
+    a.adv, a.value_preds, a.returns, a.mask = adv.data_ptr(), value_preds.data_ptr(), returns.data_ptr(), mask.data_ptr()
+    a.clip, a.huber_delta, a.value_loss_coef, a.flags = clip, huber_delta, value_loss_coef, flags
+    res = {}
+
+    def dest(k, shape):
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(*shape, dtype=torch.float32, device=dev)
+        assert t.shape == tuple(shape) and t.dtype == torch.float32 and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
+        res[k] = t
+        return t.data_ptr()
+
+    a.stats = dest("stats", (nA, len(L.PPO_EVAL_STATS)))
+    a.step_stats = dest("step_stats", (nA, max(T, 0), len(L.PPO_EVAL_STEP_STATS)))
+    if "ratio" in want:
+        a.ratio = dest("ratio", (nA, rows))
+    if "adv_norm" in want:
+        a.adv_norm = dest("adv_norm", (nA, stride))
+    ws = workspace(dev, max(int(lib.c.iplan_ppo_eval_workspace_bytes(nA, stride)), 8) // 4, "ppo_eval")
+    a.workspace = ws.data_ptr()
+    return a, res, (logp, entropy, values, old_logp, adv, value_preds, returns, mask, ws)
+
+
 def ac_xhat_pack(spec, rows, n_agents, ln_stats, lib=None):
     """The normalised feature rows of a PPO batch, gathered once per train() into the two fragment-major copies the
     split-bf16 fc1 kernels stream (include/iplan_hip.h: IplanAcXhatArgs).  ``ln_stats``: the (mean, rstd) table a
