@@ -13,6 +13,7 @@ import os
 
 import torch
 
+from iplan_amd import _lib as L
 from iplan_amd import ops
 from tests.oracle_checks import _grad_err
 from tests.test_split_bf16 import split3
@@ -761,3 +762,467 @@ def check_clip_adam_sizes(device, n, n_nets=5, steps=3, max_norm=1.0, lr=1e-2, e
         assert _rel1(arena.data[:, :n], p64) < 1e-6, ("parameters", n, step, _rel1(arena.data[:, :n], p64))
         assert torch.equal(arena.grad[:, n:].cpu(), gpad[:, n:]) and torch.equal(arena.data[:, n:].cpu(), p0[:, n:]), "floats between the nets were written"
     return worst
+
+
+# ------------------------------------------------------------------------------------------------ GAT forward + backward kernels
+# iplan_gat_fwd (save=True) + iplan_gat_bwd + the Wgrad job list of ops.gat_backward, called directly.  Unlike the wgrad / mlp3 checks
+# above, e32 (the fp32 oracle's own error against fp64) is LOGGED beside the kernel's error, not asserted: at tau >= 0.25 the gumbel
+# gate is well conditioned and the bound is the flat TOL; the one tau = 0.01 case (``e32_bound=True``) uses the learner checks'
+# data-derived rule max(TOL, E32_FACTOR x e32) (tests/oracle_checks.py) and nothing tighter.
+GAT_A = 32                                                       # attention_dim == GAT_hidden_dim of the kernels
+GAT_MAX_ENTITIES = 64                                            # IPLAN_MAX_ENTITIES (include/iplan_hip.h)
+GAT_EDGE_N = (2, 3, 15, 16, 17, 32, 33, 48, 49, 63, 64)          # around every 16-ego tile boundary, the smallest and the largest scene
+GAT_WIDTHS = ((1, 0), (13, 0), (5, 1), (16, 16), (64, 64))       # iplan_gat_fwd's argument check: d0 >= 1, d1 >= 0, no upper limit
+# (B, N, d0, d1, tau, kwargs): the cases both suites run
+GAT_CASES = ([(2, N, 5, 8, 1.0, {}) for N in GAT_EDGE_N]
+             + [(2, 17, d0, d1, 1.0, {}) for d0, d1 in GAT_WIDTHS]
+             + [(B, N, 5, 8, 1.0, dict(n_nets=5)) for N in (17, 64) for B in (1, 3)]
+             + [(2, N, 5, 8, 1.0, dict(strided=True)) for N in (17, 33)]
+             + [(2, 17, 5, 8, 0.25, {})]                          # a 1 / tau applied twice or not at all cannot cancel here
+             + [(4, 55, 5, 8, 0.01, dict(e32_bound=True))])       # the shipped gate, at a size where thousands of gates average
+
+
+def gat_case_id(B, N, d0, d1, tau, kw):
+    return f"B{B}_N{N}_d{d0}+{d1}_tau{tau:g}" + "".join(f"_{k}{'' if v is True else v}" for k, v in sorted(kw.items()))
+
+
+class GatCase:
+    """``n_nets`` GAT_Nets with their own weights, inputs, gumbel samples and upstream gradient each (inputs as in
+    oracle_checks.check_gat_fwd_bwd_vs_oracle); ``strided``: src0, src1, h_prev, out and g_out are env-major tensors handed to the
+    launches as .permute(1, 0, 2, 3) views, as the rollout does"""
+
+    def __init__(self, device, B, N, d0, d1, n_nets=2, noise=True, strided=False, seed=0):
+        from iplan_amd.arena import ParamArena
+        from iplan_amd.config import default_args
+        from iplan_amd.nova.GAT_Net import GAT_Net
+        self.device, self.B, self.N, self.d0, self.d1, self.n_nets, self.strided = device, B, N, d0, d1, n_nets, strided
+        args = default_args("highway", use_cuda=torch.device(device).type == "cuda", max_vehicle_num=N)
+        torch.manual_seed(seed + 1000 * N + 10 * (d0 + d1) + n_nets)
+        self.nets = [GAT_Net(d0 + d1, args) for _ in range(n_nets)]
+        self.params = [{k: v.detach().cpu().clone() for k, v in m.state_dict().items()} for m in self.nets]
+        self.arena = ParamArena(self.nets, device)
+        gen = torch.Generator().manual_seed(seed + 1 + 1000 * N + 10 * (d0 + d1) + n_nets)
+        self.src0 = torch.rand(n_nets, B, N, d0, generator=gen) * 2 - 1
+        self.src1 = torch.rand(n_nets, B, N, d1, generator=gen) * 2 - 1 if d1 > 0 else None
+        self.h_prev = torch.randn(n_nets, B, N, GAT_A, generator=gen) * 0.1
+        u = torch.rand(n_nets, B, N, N - 1, 2, generator=gen).clamp_min(1e-20)
+        self.noise = -torch.log((-torch.log(u)).clamp_min(1e-20)) if noise else torch.zeros(n_nets, B, N, N - 1, 2)
+        self.g_out = torch.randn(n_nets, B, N, GAT_A, generator=gen)
+        self.d_src0, self.d_src1, self.d_h, self.d_g = (self._dev(t) for t in (self.src0, self.src1, self.h_prev, self.g_out))
+        self.d_noise = self.noise.to(device)
+
+    def _dev(self, t):
+        if t is None:
+            return None
+        if self.strided:
+            return t.permute(1, 0, 2, 3).contiguous().to(self.device).permute(1, 0, 2, 3)
+        return t.to(self.device)
+
+    def new_out(self):
+        if self.strided:
+            return torch.empty(self.B, self.n_nets, self.N, GAT_A, device=self.device).permute(1, 0, 2, 3)
+        return torch.empty(self.n_nets, self.B, self.N, GAT_A, device=self.device)
+
+    def run(self, tau, out=None):
+        """forward (save=True) + backward into self.arena.grad; returns (out, saved)"""
+        out, saved = ops.gat_forward(self.arena, self.d_src0, self.d_src1, self.d_h, self.d_noise, tau=tau, save=True,
+                                     out=self.new_out() if out is None else out)
+        ops.gat_backward(self.arena, saved, self.d_g)
+        _sync(self.device)
+        return out, saved
+
+    def reference(self, n, tau, dtype):
+        """net n through the oracle under autograd: (out [B*N, A], internals incl. q k v, {name: gradient})"""
+        from oracle import iplan_oracle as O
+        from tests.oracle_checks import _req
+        B, N = self.B, self.N
+        p = _req(self.params[n], dtype)
+        obs = self.src0[n] if self.src1 is None else torch.cat([self.src0[n], self.src1[n]], -1)
+        out, it = O.gat_forward(p, obs.to(dtype), self.h_prev[n].reshape(B * N, GAT_A).to(dtype), self.noise[n].reshape(-1, 2).to(dtype),
+                                tau=tau, return_internals=True)
+        (out * self.g_out[n].reshape(B * N, GAT_A).to(dtype)).sum().backward()
+        with torch.no_grad():
+            h = it["h"]
+            v = torch.relu(h @ p["v.weight"].t() + p["v.bias"])
+            it = {k: t.detach() for k, t in it.items()}
+            it["qkv"] = torch.cat([h @ p["q.weight"].t(), h @ p["k.weight"].t(), v], -1)
+        return out.detach(), it, {k: p[k].grad for k in p}
+
+
+def check_gat_kernels(device, B, N, d0, d1, tau, n_nets=2, noise=True, strided=False, e32_bound=False):
+    """ops.gat_forward(save=True) + ops.gat_backward of ``n_nets`` independent nets against oracle.gat_forward under fp64 autograd,
+    EVERY net (the last one sits at the arena's end): out and the saved soft / hard / qkv / x / h_enc at TOL x max(1, |ref|), every
+    parameter gradient at TOL of the tensor's own maximum (no floor of 1), nothing NaN or Inf.
+    ``e32_bound`` (the tau = 0.01 case only): gradients exactly as oracle_checks.check_gat_fwd_bwd_vs_oracle holds them -- error
+    relative to max(1, |ref|), bound max(TOL, E32_FACTOR x the fp32 oracle's own worst error) -- and the saved gate and what it
+    feeds (hard, x, out) at max(TOL, E32_FACTOR x the fp32 oracle's error on that tensor): d gate / d logit = 100 gate (1 - gate)."""
+    from tests.oracle_checks import E32_FACTOR
+    case = GatCase(device, B, N, d0, d1, n_nets, noise, strided)
+    out, saved = case.run(tau)
+    what = gat_case_id(B, N, d0, d1, tau, dict(n_nets=n_nets, strided=strided))
+    worst = {}
+    assert torch.isfinite(out).all(), (what, "out is not finite")
+    for n in range(n_nets):
+        o64, it64, g64 = case.reference(n, tau, torch.float64)
+        o32, it32, g32 = case.reference(n, tau, torch.float32)
+        got = dict(out=out[n].reshape(B * N, GAT_A), soft=saved["soft"][n].view(B, N, N - 1), hard=saved["hard"][n].view(B, N, N - 1),
+                   qkv=saved["qkv"][n].view(B, N, 3 * GAT_A), x=saved["x"][n].view(B, N, GAT_A), h=saved["h_enc"][n].view(B, N, GAT_A))
+        it64["out"], it32["out"] = o64, o32
+        for k, t in got.items():
+            err, e32 = _rel1(t, it64[k]), _rel1(it32[k], it64[k])
+            print(what, "net", n, k, "err", err, "fp32 oracle", e32)
+            _worse(worst, k, err)
+            _worse(worst, k + "_fp32_oracle_vs_fp64", e32)
+            bound = max(TOL, E32_FACTOR * e32) if (e32_bound and k in ("hard", "x", "out")) else TOL
+            assert err <= bound, (what, "net", n, k, err, bound)
+        floor = 1.0 if e32_bound else 1e-30
+        scale = {k: max(g64[k].abs().max().item(), floor) for k in g64}
+        e32 = max((g32[k].double() - g64[k]).abs().max().item() / scale[k] for k in g64)
+        _worse(worst, "fp32_oracle_grad_vs_fp64", e32)
+        gtol = max(TOL, E32_FACTOR * e32) if e32_bound else TOL
+        for k in g64:
+            g = case.arena.grad_of(n, k).cpu()
+            assert torch.isfinite(g).all(), (what, "net", n, k, "gradient is not finite")
+            err = (g.double() - g64[k]).abs().max().item() / scale[k]
+            print(what, "net", n, k, "grad err", err, "of max", g64[k].abs().max().item())
+            _worse(worst, "grad", err)
+            assert err <= gtol, (what, "net", n, k, err, gtol, "fp32 oracle", e32)
+    return worst
+
+
+def _sentinel(n):
+    """n floats exact in fp32, no two neighbours alike, the size of the results"""
+    return 0.5 + (torch.arange(n, dtype=torch.float32) % 1021) / 1024.0
+
+
+def _rehome_grads(arenas, device, fill=None, pad=64):
+    """the gradient arenas of ``arenas`` back to back inside ONE buffer with ``pad`` guard floats at either end (what
+    ParamArena.colocate_grads does for the GAT + prediction-decoder pair), pre-filled with the sentinel pattern or with ``fill``.
+    Returns (buffer, its initial content on the CPU, [(start, stop) of each arena's region])."""
+    total = sum(a.grad.numel() for a in arenas) + 2 * pad
+    init = _sentinel(total) if fill is None else torch.full((total,), fill)
+    big = init.clone().to(device)
+    spans, o = [], pad
+    for a in arenas:
+        n = a.grad.numel()
+        a.grad = big[o:o + n].view(a.n_nets, a.size)
+        spans.append((o, o + n))
+        o += n
+    return big, init, spans
+
+
+def _param_slots(arena):
+    """bool [n_nets, size]: the floats of the gradient arena that belong to a parameter (the rest pads tensors to 16 bytes)"""
+    own = torch.zeros(arena.n_nets, arena.size, dtype=torch.bool)
+    for o, n in arena.ranges():
+        own[:, o:o + n] = True
+    return own
+
+
+def _bits_equal(a, b):
+    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
+
+
+def _decoder_arena(device, d, P, n_nets):
+    from iplan_amd.arena import ParamArena
+    from iplan_amd.nova.prediction_net import Prediction_Decoder
+    mods = [Prediction_Decoder(input_size=d, hidden_size=32, output_size=d, num_layers=1, pred_length=P, teacher_forcing_ratio=0, dropout=0.0)
+            for _ in range(n_nets)]
+    params = [{k: v.detach().cpu().clone() for k, v in m.state_dict().items()} for m in mods]
+    return ParamArena(mods, device), params
+
+
+def check_gat_ownership_and_repeatability(device, B=1, N=17, n_nets=2, tau=1.0):
+    """``out`` and the GAT gradient arena inside larger sentinel-filled buffers (the gradient arena followed by a prediction-decoder
+    arena, as the learner colocates them): after forward + backward the guard floats, the decoder's region and the padding between
+    the GAT's tensors are bit-unchanged; pre-filled with NaN instead, no NaN is left in ``out`` or in any GAT parameter's gradient
+    (gat_backward fills the gradient, it does not accumulate).  Three runs on the same inputs are bit-identical: the backward
+    has no atomics -- per-wave partials are reduced in a fixed order (gat_whh_grad_kernel, phase E, wgrad.hip)."""
+    case = GatCase(device, B, N, 5, 8, n_nets, seed=3)
+    dec_arena, _ = _decoder_arena(device, 5, 3, n_nets)
+    pad, n_out = 64, n_nets * B * N * GAT_A
+    runs = []
+    for fill in (None, float("nan"), None):
+        big, init, (gat_span, dec_span) = _rehome_grads([case.arena, dec_arena], device, fill)
+        out_init = _sentinel(n_out + 2 * pad) if fill is None else torch.full((n_out + 2 * pad,), fill)
+        out_buf = out_init.clone().to(device)
+        out, _ = case.run(tau, out=out_buf[pad:pad + n_out].view(n_nets, B, N, GAT_A))
+        got, got_out = big.cpu(), out_buf.cpu()
+        own = torch.zeros(big.numel(), dtype=torch.bool)
+        own[gat_span[0]:gat_span[1]] = _param_slots(case.arena).flatten()
+        assert not torch.isnan(got[own]).any(), "a GAT parameter's gradient was left unwritten"
+        assert not torch.isnan(got_out[pad:pad + n_out]).any(), "an element of out was left unwritten"
+        assert _bits_equal(got[~own], init[~own]), "gat_backward wrote outside the GAT parameters' gradient slots"
+        assert _bits_equal(got_out[:pad], out_init[:pad]) and _bits_equal(got_out[pad + n_out:], out_init[pad + n_out:]), "out's guards were written"
+        runs.append((got_out[pad:pad + n_out], got[own]))
+    for o, g in runs[1:]:
+        assert torch.equal(o, runs[0][0]), "out differs between runs on the same inputs"
+        assert torch.equal(g, runs[0][1]), "the GAT gradients differ between runs on the same inputs"
+    return {}
+
+
+def _refused(fn, needle):
+    try:
+        fn()
+    except L.IplanError as e:
+        assert needle in str(e), (needle, str(e))
+        return
+    raise AssertionError(("an invalid argument was accepted", needle))
+
+
+def check_gat_pdec_bad_arguments(device):
+    """the entry points' own argument checks, and nothing they do not reject: iplan_gat_fwd refuses N = 1 and N = IPLAN_MAX_ENTITIES
+    + 1 (csrc/gat.hip: check_gat, N outside [2, 64]); iplan_pdec_fwd refuses d = 17, d = 0, rows % N != 0 and P = 0 (csrc/preddec.hip:
+    check_pdec).  The refusal comes before the launch: the outputs keep their sentinel, and the same descriptor with the field
+    restored gives the first run's bits."""
+    lib = ops._lib(None)
+    stream = L.current_stream(device)
+    case = GatCase(device, 1, 3, 5, 8, 1, seed=5)
+    good, saved = ops.gat_forward(case.arena, case.d_src0, case.d_src1, case.d_h, case.d_noise, tau=1.0, save=True)
+    _sync(device)
+    good = good.clone()
+    a = saved["_args"]
+    sent = _sentinel(good.numel())
+    buf = sent.clone().to(device)
+    a.out = buf.data_ptr()
+    for N in (1, GAT_MAX_ENTITIES + 1):
+        a.N = N
+        _refused(lambda: lib.call("iplan_gat_fwd", a, stream), "outside [2,")
+    _sync(device)
+    assert _bits_equal(buf, sent), "a refused iplan_gat_fwd wrote its output"
+    a.N = 3
+    lib.call("iplan_gat_fwd", a, stream)
+    _sync(device)
+    assert torch.equal(buf.view_as(good), good)
+
+    pc = PdecCase(device, 3, 5, 5, 5, 2, None, None, "ones")
+    fwd = pc.forward()
+    _sync(device)
+    a = fwd["_args"]
+    bufs = {}
+    for k in ("pred", "loss"):
+        bufs[k] = (_sentinel(fwd[k].numel()), _sentinel(fwd[k].numel()).to(device))
+        setattr(a, k, bufs[k][1].data_ptr())
+    for field, bad in (("d", 17), ("d", 0), ("N", 4), ("P", 0)):            # (15 rows: N = 4 does not divide them)
+        keep = getattr(a, field)
+        setattr(a, field, bad)
+        _refused(lambda: lib.call("iplan_pdec_fwd", a, stream), "unsupported dims")
+        setattr(a, field, keep)
+    _sync(device)
+    for k, (sent, buf) in bufs.items():
+        assert _bits_equal(buf, sent), (k, "a refused iplan_pdec_fwd wrote its output")
+    lib.call("iplan_pdec_fwd", a, stream)
+    _sync(device)
+    for k, (_, buf) in bufs.items():
+        assert torch.equal(buf.view_as(fwd[k]), fwd[k]), k
+    return {}
+
+
+# ------------------------------------------------------------------------------------------------ prediction decoder kernels
+# iplan_pdec_fwd / iplan_pdec_loss / iplan_pdec_bwd + the Wgrad job list of ops.pdec_backward, called directly.  16 rows per wave, 4
+# waves (64 rows) per workgroup, rows = S * N, d <= 16.  No gate on this path: the bound is the flat TOL.
+KINK_MARGIN = 1e-4          # min |target - pred| of the draw: the L1 loss is not differentiable at 0 (asserted, never masked out)
+
+
+def _pdec_geometry():
+    from tests.predict_checks import KERNEL_CASES
+    # + 64 rows = exactly one workgroup; 65 rows with N = 5, so that row / N crosses sample boundaries inside a tile; d = 1
+    return list(KERNEL_CASES) + [(4, 16, 5, 5, 2), (13, 5, 5, 5, 2), (3, 5, 5, 1, 2), (5, 13, 12, 1, 5)]
+
+
+PDEC_GEOMETRY = _pdec_geometry()
+PDEC_OPTION_SHAPES = [(3, 5, 5, 5, 2), (5, 13, 5, 5, 5)]         # 15 rows; 65 rows, ragged, five nets
+PDEC_TEACHERS = (None, "ones", "zeros", "mixed")
+PDEC_MASKS = ("ones", "random", "zero_net")
+# seeds at which a case's draw keeps KINK_MARGIN (found on the CPU from the fp64 reference alone; 0 where not listed)
+PDEC_SEEDS = {
+    "S3_N5_P12_d16_n5_keep0_teacher-none_mask-ones": 1,
+    "S4_N16_P5_d5_n2_keep0_teacher-none_mask-ones": 1,
+    "S5_N13_P12_d1_n5_keep0_teacher-none_mask-ones": 2,
+    "S5_N13_P5_d5_n5_keep1_teacher-ones_mask-random": 1,
+    "S5_N13_P5_d5_n5_keep0_teacher-mixed_mask-ones": 1,
+}
+# (S, N, P, d, n_nets, keep, teacher, mask_kind, mask_sum): the cases both suites run
+PDEC_CASES = ([g + (False, None, "ones", False) for g in PDEC_GEOMETRY]
+              + [g + (keep, t, "random", False) for g in PDEC_OPTION_SHAPES for keep in (False, True) for t in PDEC_TEACHERS]
+              + [g + (False, "mixed", m, False) for g in PDEC_OPTION_SHAPES for m in ("ones", "zero_net")]     # ("random": in the cross above)
+              + [(5, 13, 5, 5, 5, True, t, "random", True) for t in (None, "mixed")])
+
+
+def pdec_case_id(S, N, P, d, n_nets, keep, teacher, mask_kind, mask_sum=False):
+    return f"S{S}_N{N}_P{P}_d{d}_n{n_nets}_keep{int(bool(keep))}_teacher-{teacher or 'none'}_mask-{mask_kind}" + ("_masksum" if mask_sum else "")
+
+
+class PdecCase:
+    """random decoder parameters and inputs per net; targets continuous and uniform in [-1, 1].  ``keep``: Bernoulli(0.9) flags with
+    drop_p = 0.1, or None; ``teacher``: None, "ones", "zeros", or "mixed" -- a pattern that differs per net: net 0 teaches the even
+    steps, the last net only the final step (whose flag must change nothing), the nets between a random draw with a 0 and a 1;
+    ``mask_kind``: "ones", "random" (0/1, at least one of each) or "zero_net" (random, all zeros for net 0 of several);
+    ``mask_sum``: the injected normaliser, 1.7 x the mask's own sum (0.5 for a net whose mask is all zeros)"""
+
+    def __init__(self, device, S, N, P, d, n_nets, keep, teacher, mask_kind, mask_sum=False, seed=None):
+        self.device, self.S, self.N, self.P, self.d, self.n_nets = device, S, N, P, d, n_nets
+        self.id = pdec_case_id(S, N, P, d, n_nets, keep, teacher, mask_kind, mask_sum)
+        seed = PDEC_SEEDS.get(self.id, 0) if seed is None else seed
+        rows = self.rows = S * N
+        torch.manual_seed(seed + 1000 * S + 100 * N + 10 * P + d + n_nets)
+        self.arena, self.params = _decoder_arena(device, d, P, n_nets)
+        gen = torch.Generator().manual_seed(seed + 7 + S + N + P + d)
+        self.x0 = torch.rand(n_nets, rows, d, generator=gen) * 2 - 1
+        self.h0 = torch.randn(n_nets, rows, 32, generator=gen) * 0.5
+        self.target = torch.rand(n_nets, rows, P, d, generator=gen) * 2 - 1
+        self.drop_p = 0.1 if keep else 0.0
+        self.keep = (torch.rand(n_nets, P, rows, 32, generator=gen) < 0.9).float() if keep else None
+        if mask_kind == "ones":
+            self.mask = torch.ones(n_nets, S)
+        else:
+            assert S >= 2
+            self.mask = (torch.rand(n_nets, S, generator=gen) < 0.6).float()
+            self.mask[:, 0], self.mask[:, 1] = 1.0, 0.0
+            if mask_kind == "zero_net":
+                assert n_nets > 1
+                self.mask[0] = 0.0
+        self.teacher = None
+        if teacher == "ones":
+            self.teacher = torch.ones(n_nets, P, dtype=torch.int32)
+        elif teacher == "zeros":
+            self.teacher = torch.zeros(n_nets, P, dtype=torch.int32)
+        elif teacher == "mixed":
+            t = torch.randint(0, 2, (n_nets, P), generator=gen, dtype=torch.int32)
+            if P > 1:
+                t[:, 0], t[:, 1] = 1, 0
+            t[0] = (torch.arange(P) % 2 == 0).to(torch.int32)
+            t[-1] = 0
+            t[-1, P - 1] = 1
+            self.teacher = t
+        self.mask_sum = None
+        if mask_sum:
+            s = self.mask.sum(1)
+            self.mask_sum = torch.where(s > 0, 1.7 * s, torch.full_like(s, 0.5))
+        dev = lambda t: None if t is None else t.to(device)  # noqa: E731
+        self.d_x0, self.d_h0, self.d_target, self.d_mask, self.d_keep, self.d_teacher, self.d_mask_sum = (
+            dev(t) for t in (self.x0, self.h0, self.target, self.mask, self.keep, self.teacher, self.mask_sum))
+
+    def forward(self, teacher="own"):
+        return ops.pdec_forward(self.arena, self.d_x0, self.d_h0, self.d_target, self.d_mask, self.N, keep=self.d_keep, drop_p=self.drop_p,
+                                teacher=self.d_teacher if isinstance(teacher, str) else teacher, mask_sum=self.d_mask_sum)
+
+    def run(self, teacher="own"):
+        fwd = self.forward(teacher)
+        g_h0 = ops.pdec_backward(self.arena, fwd)
+        _sync(self.device)
+        return fwd, g_h0
+
+    def reference(self, n, dtype):
+        """net n as a plain loop over the oracle's decoder step: (pred [rows, P, d], loss, {name: gradient}, dLoss/dh0)"""
+        from oracle import iplan_oracle as O
+        from tests.oracle_checks import _req
+        S, N, P, d, rows = self.S, self.N, self.P, self.d, self.rows
+        p = _req(self.params[n], dtype)
+        dp = O.strip_prefix(p, "decoder.")
+        h0 = self.h0[n].to(dtype).requires_grad_(True)
+        target = self.target[n].to(dtype)
+        x, h, preds = self.x0[n].to(dtype).reshape(rows, 1, d), h0, []
+        for s in range(P):
+            y, h = O.decoder_forward(dp, x, h, None if self.keep is None else self.keep[n, s].to(dtype).reshape(rows, 1, 32), self.drop_p)
+            preds.append(y)
+            x = target[:, s:s + 1] if (self.teacher is not None and int(self.teacher[n, s]) != 0) else y
+        pred = torch.cat(preds, 1)
+        mask_over = self.mask[n].to(dtype)[:, None, None, None].expand(S, N, P, d).reshape(rows, P, d)
+        if self.mask_sum is None:
+            loss = O.masked_l1(target, pred, mask_over, d * P)
+        else:
+            loss = (torch.abs(target - pred) * mask_over).sum() / (self.mask_sum[n].to(dtype) * (N * P * d) + O.EPS) * (d * P)
+        loss.backward()
+        return pred.detach(), loss.detach(), {k: p[k].grad for k in p}, h0.grad
+
+
+def check_pdec_kernels(device, S, N, P, d, n_nets, keep, teacher, mask_kind, mask_sum=False, seed=None):
+    """ops.pdec_forward + ops.pdec_backward against the fp64 loop (PdecCase.reference), every net: pred and loss at TOL x max(1, |ref|),
+    every decoder parameter's gradient and g_h0 = dLoss/dh0 at TOL of the tensor's own maximum; the fp32 loop's own error is logged
+    beside each.  A net whose mask is all zeros has loss 0 and gradients that are exactly 0 (and finite); every masked-out sample's
+    rows of g_h0 are exactly 0."""
+    case = PdecCase(device, S, N, P, d, n_nets, keep, teacher, mask_kind, mask_sum, seed)
+    fwd, g_h0 = case.run()
+    worst = {}
+    margin = float("inf")
+    for n in range(n_nets):
+        pred64, loss64, g64, gh64 = case.reference(n, torch.float64)
+        pred32, loss32, g32, gh32 = case.reference(n, torch.float32)
+        margin = min(margin, (case.target[n].double() - pred64).abs().min().item())
+        assert margin > KINK_MARGIN, (case.id, "the draw puts a target on the L1 kink: change the seed (PDEC_SEEDS)", n, margin)
+        for key, got, r64, r32 in (("pred", fwd["pred"][n], pred64, pred32), ("loss", fwd["loss"][n], loss64, loss32)):
+            err = _rel1(got, r64)
+            _worse(worst, key, err)
+            _worse(worst, key + "_e32", _rel1(r32, r64))
+            assert torch.isfinite(got).all() and err <= TOL, (case.id, key, "net", n, err)
+        live = case.mask[n].sum() > 0
+        named = [(k, case.arena.grad_of(n, k), g64[k], g32[k]) for k in g64] + [("g_h0", g_h0[n], gh64, gh32)]
+        for k, got, r64, r32 in named:
+            got = got.cpu()
+            assert torch.isfinite(got).all(), (case.id, k, "net", n, "not finite")
+            if not live:
+                assert torch.equal(got, torch.zeros_like(got)), (case.id, k, "net", n, "gradient of an all-masked net is not exactly 0")
+                continue
+            err = _grad_err(got, r64)
+            print(case.id, "net", n, k, "err", err, "e32", _grad_err(r32, r64))
+            _worse(worst, "g_h0" if k == "g_h0" else "grad", err)
+            _worse(worst, ("g_h0" if k == "g_h0" else "grad") + "_e32", _grad_err(r32, r64))
+            assert err <= TOL, (case.id, k, "net", n, err)
+        if not live:
+            assert float(fwd["loss"][n]) == 0.0 and float(loss64) == 0.0, (case.id, "loss of an all-masked net", n)
+        dead = (case.mask[n] == 0)[:, None].expand(S, N).reshape(S * N)
+        rows_dead = g_h0[n].cpu()[dead]
+        assert torch.equal(rows_dead, torch.zeros_like(rows_dead)), (case.id, "a masked-out sample contributes to g_h0", n)
+    worst["kink_margin"] = margin
+    return worst
+
+
+def check_pdec_teacher_identities(device):
+    """``teacher`` all zeros is bit-identical to teacher=None (pred, loss, gradients, g_h0); so is all ones at P = 1, where the only
+    flag is the last step's and feeds nothing"""
+    for (S, N, P, d, n_nets), flag in (((5, 13, 5, 5, 5), 0), ((1, 17, 1, 4, 2), 1)):
+        results = []
+        for teacher in (None, torch.full((n_nets, P), flag, dtype=torch.int32, device=device)):
+            case = PdecCase(device, S, N, P, d, n_nets, True, None, "random" if S > 1 else "ones")
+            fwd, g_h0 = case.run(teacher)
+            results.append((fwd["pred"].cpu(), fwd["loss"].cpu(), case.arena.grad.cpu().clone(), g_h0.cpu()))
+        for name, a, b in zip(("pred", "loss", "grad", "g_h0"), *results):
+            assert torch.equal(a, b), ((S, N, P, d, n_nets), "teacher flags", flag, name, "differs from teacher=None")
+    return {}
+
+
+def check_pdec_ownership(device, S=1, N=17, P=5, d=5, n_nets=2):
+    """17 rows (a ragged second tile), two nets.  The decoder's gradient arena sits behind a GAT arena inside one sentinel-filled
+    buffer, as the learner colocates them: pdec_backward leaves the guards, the GAT's region and the padding between the decoder's
+    tensors bit-unchanged, and -- the buffer pre-filled with NaN -- leaves no NaN in any decoder parameter's gradient (it fills,
+    it does not accumulate).  pred, loss and g_h0 are allocated by the ops themselves: blocks of their sizes are filled with NaN
+    and handed back to the allocator first, so that an element the kernels do not write would surface as a NaN (a caching
+    allocator returns exactly those blocks; where it does not, this part checks nothing and costs nothing)."""
+    from iplan_amd.arena import ParamArena
+    from iplan_amd.config import default_args
+    from iplan_amd.nova.GAT_Net import GAT_Net
+    case = PdecCase(device, S, N, P, d, n_nets, True, "mixed", "ones")
+    args = default_args("highway", use_cuda=torch.device(device).type == "cuda", max_vehicle_num=N)
+    gat_arena = ParamArena([GAT_Net(13, args) for _ in range(n_nets)], device)
+    rows = S * N
+    runs = []
+    for fill in (None, float("nan")):
+        big, init, (gat_span, dec_span) = _rehome_grads([gat_arena, case.arena], device, fill)
+        junk = [torch.full((n,), float("nan"), device=device) for n in
+                (n_nets * rows * P * d, n_nets * rows * P * L.PDEC_SAVE, n_nets * ((rows + 15) // 16), n_nets, n_nets * rows * P * L.PDEC_DSAVE,
+                 n_nets * rows * 32)]
+        _sync(device)
+        del junk
+        fwd, g_h0 = case.run()
+        for k, t in (("pred", fwd["pred"]), ("loss", fwd["loss"]), ("g_h0", g_h0)):
+            assert torch.isfinite(t).all(), (k, "has elements the kernels did not write")
+        got = big.cpu()
+        own = torch.zeros(big.numel(), dtype=torch.bool)
+        own[dec_span[0]:dec_span[1]] = _param_slots(case.arena).flatten()
+        assert not torch.isnan(got[own]).any(), "a decoder parameter's gradient was left unwritten"
+        assert _bits_equal(got[~own], init[~own]), "pdec_backward wrote outside the decoder parameters' gradient slots"
+        runs.append((fwd["pred"].cpu(), fwd["loss"].cpu(), g_h0.cpu(), got[own]))
+    for a, b in zip(*runs):
+        assert torch.equal(a, b), "the decoder kernels' results depend on what their buffers held before"
+    return {}

@@ -3,7 +3,9 @@ runs through the host emulator, on the gfx950 build, where the MFMA operand layo
 the cross-lane reductions and the grid geometry are the hardware's: every wgrad job shape at the edges of its chunk geometry
 (incl. the row counts at which the virtual chunks reach their target, and the mixed launch whose wide chunks are trimmed as in
 production), wgrad one product at a time, its fixed reduction order, mlp3, the actor / critic backward, the optimiser kernels,
-and the rollout body in config 1's feature layout (GAT and behaviour off).
+the rollout body in config 1's feature layout (GAT and behaviour off), and the prediction learner's four kernels alone: GAT
+forward + backward at every tile edge of the entity count with a well-conditioned gate (tau = 1, 0.25), the prediction decoder
+with its teacher / mask_sum / keep arguments.
 Worst errors are logged the way tests/test_gpu_parity_fullsize.py logs its own (copied to profiles/ as the tolerance evidence)."""
 import os
 
@@ -110,6 +112,33 @@ def test_adam_weight_decay():
 @pytest.mark.parametrize("n", KC.ADAM_SIZES)
 def test_clip_adam_sizes(n):
     _log(f"kernel_clip_adam_n{n}", KC.check_clip_adam_sizes(DEV, n))
+
+
+@pytest.mark.parametrize("case", KC.GAT_CASES, ids=lambda c: KC.gat_case_id(*c))
+def test_gat_kernels_vs_fp64(case):
+    B, N, d0, d1, tau, kw = case
+    _log("kernel_gat_" + KC.gat_case_id(*case), KC.check_gat_kernels(DEV, B, N, d0, d1, tau, **kw))
+
+
+def test_gat_kernels_write_what_they_own_and_repeat():
+    _log("kernel_gat_ownership_repeatability", KC.check_gat_ownership_and_repeatability(DEV))
+
+
+@pytest.mark.parametrize("case", KC.PDEC_CASES, ids=lambda c: KC.pdec_case_id(*c))
+def test_pdec_kernels_vs_fp64(case):
+    _log("kernel_pdec_" + KC.pdec_case_id(*case), KC.check_pdec_kernels(DEV, *case))
+
+
+def test_pdec_teacher_flags_that_change_nothing():
+    _log("kernel_pdec_teacher_identities", KC.check_pdec_teacher_identities(DEV))
+
+
+def test_pdec_kernels_write_what_they_own():
+    _log("kernel_pdec_ownership", KC.check_pdec_ownership(DEV))
+
+
+def test_gat_pdec_bad_arguments_are_refused():
+    _log("kernel_gat_pdec_bad_arguments", KC.check_gat_pdec_bad_arguments(DEV))
 
 
 def test_rollout_body_config1_vs_oracle():
