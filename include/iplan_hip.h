@@ -972,6 +972,65 @@ typedef struct {
 int iplan_ac_trace(const IplanAcTraceArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Policy saliency: the gradient of an actor's log-probability and of a critic's value with respect to the INPUT row
+ *   x = [ per entity: hist || att || beh ] || onehot(last action) || onehot(agent)      (the comment above IplanAcNet)
+ * for E*S independent rows in one launch, forward + input-backward.  Row r = e*S + s is described by `feat` as for iplan_ac_trace
+ * (feat.T must equal S; features at physical row e*T_phys + s; last action from feat.last_action / last_action64, -1 = none).  The
+ * row's GRU state is GIVEN -- 64 floats at h + net*hs_net + e*hs_chain + s*hs_step -- and held constant: nothing is differentiated
+ * through time.  Differentiated is
+ *   actor   y = log_softmax(masked logits)[a*]   masked logits are the constant -1e10 and carry no gradient; a* = the row's entry of
+ *               `target` (target[net*tg_s_net + e*tg_s_chain + s*tg_s_step]; NULL: target_all for every row), or the row's own
+ *               argmax -- lowest index on ties, as iplan_ac_trace's greedy -- where that entry is -1.  target_all is checked on the
+ *               host against [-1, n_actions); the entries of `target` live on the device: one outside [0, n_actions) is read as -1.
+ *   critic  y = V
+ * back through head, LN, the GRU cell with respect to its input only (d gi -> W_ih^T), LN, act', fc2^T, LN, act', fc1^T and the
+ * whole LayerNorm(F):  dx = (g^ - mean g^ - x^ mean(g^ x^)) / sigma,  g^ = gamma * (W1^T delta).  One wave per 16-row tile, four
+ * tiles per workgroup; fc1 and fc1^T on v_mfma_f32_16x16x4_f32; the F axis is passed over five times (mean, variance, fc1, the two
+ * means of g^, dx) with W1^T delta recomputed in the last pass -- nothing F-wide is kept.  avail: int32 at avail + net*av_s_net +
+ * e*av_s_chain + s*av_s_step (NULL = all available).  packed_*: as in IplanAcTraceArgs (same bits as the arena in place).
+ * Outputs, each optional (NULL = not written), contiguous, of the nets `which` selects; at least one must be asked for:
+ *   logp, values  [n_agents, E*S]            y of the actors / the critics
+ *   target_out    [n_agents, E*S] int64      the a* that was used
+ *   entity_*      [n_agents, E*S, N, n_src, 2]   per entity and ENABLED source (w[k] > 0, in order): sum_k g_k x_k and sum_k |g_k|
+ *                                            over the source's w[k] columns of that entity, added one by one in column order
+ *   input_grad_*  [n_agents, E*S, F]         the whole gradient in the reference's entity-major column order, one-hots included
+ *   act1_*, act2_* [n_agents, E*S, 64]       the two post-activation tiles of the trunk (the ReLU branch taken; for tests)
+ * No atomics, no cross-row sums: a row's results do not depend on the lane, tile or workgroup it falls in.  Parameter and gradient
+ * memory is only read.  N <= IPLAN_MAX_ENTITIES, 1 <= n_actions <= 16; act1 / act2 and the packed operands 16-byte aligned.
+ */
+typedef struct {
+    int32_t n_agents, E, S;
+    int32_t which;              /* 0 = actors, 1 = critics, 2 = both                                       */
+    int32_t act_tanh;           /* MLPBase activation: 0 = ReLU, 1 = tanh                                  */
+    int32_t target_all;         /* used when target == NULL: -1 = greedy, else one action for every row    */
+    IplanAcFeatures feat;
+    IplanAcNet actor, critic;
+    const float* h_actor;
+    const float* h_critic;
+    int64_t hs_net, hs_chain, hs_step;
+    const int32_t* avail;
+    int64_t av_s_net, av_s_chain, av_s_step;
+    const int64_t* target;
+    int64_t tg_s_net, tg_s_chain, tg_s_step;
+    const float* packed_actor;
+    const float* packed_critic;
+    int64_t packed_s_net;
+    float* logp;
+    float* values;
+    int64_t* target_out;
+    float* entity_actor;
+    float* entity_critic;
+    float* input_grad_actor;
+    float* input_grad_critic;
+    float* act1_actor;
+    float* act2_actor;
+    float* act1_critic;
+    float* act2_critic;
+} IplanAcSaliencyArgs;
+
+int iplan_ac_saliency(const IplanAcSaliencyArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Three-layer perceptron of the FC behaviour ablation (nova/behavior_FC_net.py:6-37, Encoder_3FC / Decoder_3FC):
  *   out = [softmax] (W3 tanh(W2 tanh(W1 x + b1) + b2) + b3)   for n_nets stacked nets, rows per net.
  * off[0..5] = linear_1.weight [H,K0], linear_1.bias, linear_2.weight [H,H], linear_2.bias, out.weight [O,H], out.bias.

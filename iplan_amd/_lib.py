@@ -53,7 +53,7 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_pdec_fwd", "iplan_pdec_bwd", "iplan_beh_fwd", "iplan_beh_bwd", "iplan_mlp3_fwd", "iplan_mlp3_bwd", "iplan_seq2seq_fwd", "iplan_ac_pack_fc1",
                 "iplan_ac_xhat_pack", "iplan_ac_fc1_split_fwd", "iplan_ac_bwd_fc1_split",
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
-                "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval"]
+                "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -444,6 +444,20 @@ class AcTraceArgs(C.Structure):
     ]
 
 
+class AcSaliencyArgs(C.Structure):
+    _fields_ = [
+        ("n_agents", i32), ("E", i32), ("S", i32), ("which", i32), ("act_tanh", i32), ("target_all", i32),
+        ("feat", AcFeatures), ("actor", AcNet), ("critic", AcNet),
+        ("h_actor", fp), ("h_critic", fp), ("hs_net", i64), ("hs_chain", i64), ("hs_step", i64),
+        ("avail", fp), ("av_s_net", i64), ("av_s_chain", i64), ("av_s_step", i64),
+        ("target", fp), ("tg_s_net", i64), ("tg_s_chain", i64), ("tg_s_step", i64),
+        ("packed_actor", fp), ("packed_critic", fp), ("packed_s_net", i64),
+        ("logp", fp), ("values", fp), ("target_out", fp),
+        ("entity_actor", fp), ("entity_critic", fp), ("input_grad_actor", fp), ("input_grad_critic", fp),
+        ("act1_actor", fp), ("act2_actor", fp), ("act1_critic", fp), ("act2_critic", fp),
+    ]
+
+
 # ---- FC behaviour ablation -------------------------------------------------------------------------------
 class Mlp3Args(C.Structure):
     _fields_ = [
@@ -480,4 +494,5 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanPdecArgs": PdecArgs, "IplanBehArgs": BehArgs, "IplanMlp3Args": Mlp3Args, "IplanAdvNormArgs": AdvNormArgs, "IplanSeq2SeqArgs": Seq2SeqArgs, "IplanSeq2SeqBwdArgs": Seq2SeqBwdArgs, "IplanAcPackArgs": AcPackArgs,
                   "IplanIpcHandle": IpcHandle, "IplanP2pArgs": P2pArgs, "IplanAcXhatArgs": AcXhatArgs, "IplanAcFc1SplitArgs": AcFc1SplitArgs,
                   "IplanObsHistArgs": ObsHistArgs, "IplanPredictArgs": PredictArgs, "IplanBehEvalArgs": BehEvalArgs,
-                  "IplanGatTraceArgs": GatTraceArgs, "IplanAcTraceArgs": AcTraceArgs, "IplanPpoEvalArgs": PpoEvalArgs}
+                  "IplanGatTraceArgs": GatTraceArgs, "IplanAcTraceArgs": AcTraceArgs, "IplanPpoEvalArgs": PpoEvalArgs,
+                  "IplanAcSaliencyArgs": AcSaliencyArgs}

@@ -237,6 +237,109 @@ class DcntrlMAC:
         out = {k: res[k][:, :, 0].transpose(0, 1) for k in ("probs", "greedy", "entropy", "values")}
         return {k: v.cpu().numpy() for k, v in out.items()} if as_np else out
 
+    def saliency(self, batch, target="recorded", which="both", hidden=None, want=("entity",), steps=None):
+        """Which vehicles, and which of their inputs, drive this agent's decision and this critic's value?  The gradient of the actors'
+        log-probability log pi(a* | x) and of the critics' value V(x) with respect to the INPUT row x = [hist || att || beh per entity,
+        one-hots], one launch for all agents and rows (ops.saliency), reduced per entity and per source.  ``batch``: what
+        ``policy_trace`` takes (fields [E, S, nA, ...], torch or numpy); step s sees exactly the inputs ``policy_trace`` shows it: the
+        fields of step s, the recorded ``actions[:, s-1]`` as last action (none at s = 0), ``avail_actions[:, s]``.
+        The GRU state of row (e, s) is the RECORDED ``rnn_states_actors[:, s]`` / ``rnn_states_critics[:, s]``, or, with
+        ``hidden=(ha, hc)``, a pair of [E, S, nA, M] tensors over the selected steps.  The state is an input: it is held constant and
+        nothing is differentiated through time (no BPTT), so a row's gradient is the sensitivity of THIS step's output to THIS step's
+        observation.  ``target``: "recorded" (``actions[:, s]``), "greedy" (the row's own argmax, lowest index on ties) or an int tensor
+        [E, S, nA] (-1 = greedy for that row).  ``steps``: None = every step, a slice with step 1, or an int = that one step, returned
+        without the step axis (with an EpisodeBatch: the one-step form at t_ep).  ``which``: "actor", "critic" or "both".
+        Returns a dict, [E, S, nA, ...] each:
+          actor_gxi, critic_gxi [.., N, n_src]  sum_k g_k x_k over the source's columns of the entity (signed gradient x input)
+          actor_gl1, critic_gl1 [.., N, n_src]  sum_k |g_k| over the same columns
+          logp, values, target_action           y of the actors / critics and the a* that was used (int64)
+          sources                               the tuple of field names, the n_src axis in ``_widths()`` order
+          actor_input_grad, critic_input_grad [.., F]  with "input_grad" in ``want``: the whole gradient in the reference's column order
+          actor_act1, actor_act2, critic_act1, critic_act2 [.., M]  with "act" in ``want``: the trunk's post-activation values (tests)
+        Device tensors in -> device tensors out, numpy in -> numpy out.  Draws from no generator; parameters, gradient entries,
+        optimiser state, ``hidden_states`` and the batch are not touched; the packed fc1 operands are brought up to date exactly as
+        ``policy_trace`` does it (the values any later launch would pack), the kernel only reads them.  Not covered: layer_N /
+        recurrent_N other than 1, saliency through the GAT or the behaviour encoder back to the raw history, BPTT."""
+        a = self.args
+        if a.layer_N != 1 or a.recurrent_N != 1:
+            raise NotImplementedError("saliency covers layer_N = recurrent_N = 1 only")
+        want = tuple(want)
+        assert all(k in ("entity", "input_grad", "act") for k in want), want
+        nA, N, M = self.n_agents, a.max_vehicle_num, a.rnn_hidden_dim
+        as_np = isinstance(batch["history"], np.ndarray)
+
+        def dev(t, dtype=None):
+            return self._dev(th.as_tensor(t) if isinstance(t, np.ndarray) else t, dtype)
+
+        def field(key, dtype=None):
+            """[E, T1, ...] on the device, rows addressable as e * T1 + t (a copy only when the batch's layout is not that)"""
+            t = dev(batch[key], dtype)
+            return t if t.stride(0) == t.shape[1] * t.stride(1) and t[0, 0].is_contiguous() else t.contiguous()
+
+        hist = field("history", th.float32)
+        E, T1 = hist.shape[:2]
+        one = isinstance(steps, (int, np.integer))
+        if steps is None:
+            t0, S = 0, T1
+        elif one:
+            t0, S = int(steps), 1
+        else:
+            t0, t1, stride = steps.indices(T1)
+            assert stride == 1, "steps: a slice with step 1"
+            S = t1 - t0
+        assert 0 <= t0 and S >= 1 and t0 + S <= T1, (steps, T1)
+        sl = slice(t0, t0 + S)
+        sources = []
+        for key, w in self._widths():
+            view = (hist if key == "history" else field(key, th.float32))[:, sl]                  # [E, S, nA, N, w]
+            sources.append((view, w, view.stride(2), view.stride(1)))
+        acts = field("actions")[..., 0]                                                           # [E, T1, nA] int64
+        last, la_strides = None, (0, 0)
+        if a.obs_last_action:
+            last = th.cat([th.full_like(acts[:, :1], -1), acts[:, :-1]], 1)[:, sl]                # the action of t - 1; none at t = 0
+            la_strides = (last.stride(2), last.stride(1))
+        spec = ops.AcFeatureSpec(N, sources, n_actions=a.n_actions if a.obs_last_action else 0, last_action=last, la_strides=la_strides,
+                                 n_id=nA if a.obs_agent_id else 0, T=S, T_phys=T1)
+        assert spec.F == self.input_shape, (spec.F, self.input_shape)
+        avail = field("avail_actions")
+        if avail.dtype != th.int32:
+            avail = avail.to(th.int32)
+        avail = avail[:, sl]
+        if hidden is None:
+            ha, hc = field("rnn_states_actors", th.float32)[:, sl], field("rnn_states_critics", th.float32)[:, sl]
+        else:
+            ha, hc = (dev(h, th.float32) for h in hidden)
+        assert ha.shape == hc.shape == (E, S, nA, M), (ha.shape, hc.shape, (E, S, nA, M))
+        if ha.stride() != hc.stride() or ha.stride(3) != 1:
+            ha, hc = ha.contiguous(), hc.contiguous()
+        tgt, tgt_all = None, -1
+        if isinstance(target, str):
+            assert target in ("recorded", "greedy"), target
+            if target == "recorded":
+                tgt = acts[:, sl]
+        else:
+            tgt = dev(target, th.int64)
+            assert tgt.shape == (E, S, nA), (tgt.shape, (E, S, nA))
+        w = {"actor": 0, "critic": 1, "both": 2}[which]
+        esn = lambda t: (t.stride(2), t.stride(0), t.stride(1))                                   # noqa: E731  (net, chain, step)
+        res = ops.saliency(self.actor_arena, self.critic_arena, w, spec, E, S, nA, h_actor=ha, h_critic=hc, h_strides=esn(ha),
+                           avail=avail, avail_strides=esn(avail), target=tgt, target_strides=esn(tgt) if tgt is not None else (0, 0, 0),
+                           target_all=tgt_all, n_actions=a.n_actions, want=("y",) + want, packed=self.fc1_pack.get(spec))
+        out = {"sources": tuple(k for k, _ in self._widths())}
+        for k in ("logp", "values", "target_action"):
+            if k in res:
+                out[k] = res[k].permute(1, 2, 0)
+        for net in ("actor", "critic"):
+            if "entity_" + net in res:
+                ent = res["entity_" + net].permute(1, 2, 0, 3, 4, 5)                              # [E, S, nA, N, n_src, 2]
+                out[net + "_gxi"], out[net + "_gl1"] = ent[..., 0], ent[..., 1]
+            for k in ("input_grad", "act1", "act2"):
+                if k + "_" + net in res:
+                    out[net + "_" + k] = res[k + "_" + net].permute(1, 2, 0, 3)
+        if one:
+            out = {k: (v if k == "sources" else v[:, 0]) for k, v in out.items()}
+        return {k: (v if k == "sources" else v.cpu().numpy()) for k, v in out.items()} if as_np else out
+
     def get_value_ippo(self, agent_id, obs, rnn_states_critic):
         """controllers/dcntrl_controller.py:61-68."""
         obs_in = obs.reshape(-1, 1, obs.shape[-1])

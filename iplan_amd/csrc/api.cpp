@@ -1,4 +1,5 @@
-// C-ABI bookkeeping: version + thread-local error string; the argument checks of iplan_ppo_eval (kernels: ppo_eval.hip).
+// C-ABI bookkeeping: version + thread-local error string; the argument checks of iplan_ppo_eval (kernels: ppo_eval.hip) and of
+// iplan_ac_saliency (kernel: policy_saliency.hip).
 #include <cstring>
 
 #include "api_util.h"
@@ -9,6 +10,7 @@ char* error_buffer() {
     return buf;
 }
 int ppo_eval_launch(const IplanPpoEvalArgs& a, hipStream_t stream);   // ppo_eval.hip
+int ac_saliency_launch(const IplanAcSaliencyArgs& a, hipStream_t stream);   // policy_saliency.hip
 }  // namespace iplan
 
 extern "C" const char* iplan_last_error(void) { return iplan::error_buffer(); }
@@ -21,6 +23,7 @@ extern "C" size_t iplan_sizeof(const char* name) {
     IPLAN_SZ(IplanAcFeatures) IPLAN_SZ(IplanAcFwdArgs) IPLAN_SZ(IplanAcBwdArgs) IPLAN_SZ(IplanAdamArgs) IPLAN_SZ(IplanWgradProblem)
     IPLAN_SZ(IplanWgradArgs) IPLAN_SZ(IplanPpoPrepareArgs) IPLAN_SZ(IplanPpoLossArgs) IPLAN_SZ(IplanPdecArgs) IPLAN_SZ(IplanBehArgs) IPLAN_SZ(IplanMlp3Args) IPLAN_SZ(IplanAdvNormArgs) IPLAN_SZ(IplanSeq2SeqArgs) IPLAN_SZ(IplanAcPackArgs) IPLAN_SZ(IplanP2pArgs) IPLAN_SZ(IplanIpcHandle) IPLAN_SZ(IplanAcXhatArgs) IPLAN_SZ(IplanAcFc1SplitArgs) IPLAN_SZ(IplanObsHistArgs) IPLAN_SZ(IplanSeq2SeqBwdArgs)
     IPLAN_SZ(IplanPredictArgs) IPLAN_SZ(IplanBehEvalArgs) IPLAN_SZ(IplanGatTraceArgs) IPLAN_SZ(IplanAcTraceArgs) IPLAN_SZ(IplanPpoEvalArgs)
+    IPLAN_SZ(IplanAcSaliencyArgs)
 #undef IPLAN_SZ
     return 0;
 }
@@ -49,4 +52,39 @@ extern "C" int iplan_ppo_eval(const IplanPpoEvalArgs* a, iplan_stream_t stream) 
     if (a->adv_norm == a->adv) return fail(IPLAN_EINVAL, "iplan_ppo_eval: adv_norm must not alias adv");
     if (((size_t)a->workspace) & 7) return fail(IPLAN_EALIGN, "iplan_ppo_eval: workspace must be 8-byte aligned");
     return ppo_eval_launch(*a, (hipStream_t)stream);
+}
+
+extern "C" int iplan_ac_saliency(const IplanAcSaliencyArgs* a, iplan_stream_t stream) {
+    using namespace iplan;
+    if (!a) return fail(IPLAN_EINVAL, "iplan_ac_saliency: null args");
+    if (a->which < 0 || a->which > 2 || a->n_agents < 1) return fail(IPLAN_EINVAL, "iplan_ac_saliency: bad which=%d / n_agents=%d", a->which, a->n_agents);
+    if (a->E < 1 || a->S < 1) return fail(IPLAN_EINVAL, "iplan_ac_saliency: E=%d x S=%d rows, at least one row is needed", a->E, a->S);
+    if ((int64_t)a->E * a->S > 0x7fffffff / 16) return fail(IPLAN_EINVAL, "iplan_ac_saliency: E * S = %lld rows are too many", (long long)a->E * a->S);
+    const IplanAcFeatures& ft = a->feat;
+    if (ft.N < 1 || ft.N > IPLAN_MAX_ENTITIES) return fail(IPLAN_EINVAL, "iplan_ac_saliency: N=%d outside [1,%d]", ft.N, IPLAN_MAX_ENTITIES);
+    if (ft.T != a->S || ft.T_phys < ft.T) return fail(IPLAN_EINVAL, "iplan_ac_saliency: feat.T=%d must equal S=%d and T_phys=%d must not be smaller", ft.T, a->S, ft.T_phys);
+    if (ft.n_actions < 0 || ft.n_id < 0 || ft.w[0] < 0 || ft.w[1] < 0 || ft.w[2] < 0 || ft.N * (ft.w[0] + ft.w[1] + ft.w[2]) + ft.n_actions + ft.n_id < 1)
+        return fail(IPLAN_EINVAL, "iplan_ac_saliency: bad feature widths");
+    for (int s = 0; s < 3; ++s)
+        if (ft.w[s] > 0 && !ft.src[s]) return fail(IPLAN_EINVAL, "iplan_ac_saliency: feature source %d is null", s);
+    bool any = false;
+    if (a->which != 1) {
+        if (a->actor.n_out < 1 || a->actor.n_out > 16) return fail(IPLAN_EINVAL, "iplan_ac_saliency: n_actions=%d outside [1,16]", a->actor.n_out);
+        if (!a->actor.params) return fail(IPLAN_EINVAL, "iplan_ac_saliency: actor parameters missing");
+        if (!a->h_actor) return fail(IPLAN_EINVAL, "iplan_ac_saliency: the actors' GRU state h_actor is missing");
+        if (!a->target && (a->target_all < -1 || a->target_all >= a->actor.n_out))
+            return fail(IPLAN_EINVAL, "iplan_ac_saliency: target action %d outside [-1,%d)", a->target_all, a->actor.n_out);
+        any = any || a->logp || a->target_out || a->entity_actor || a->input_grad_actor || a->act1_actor || a->act2_actor;
+    }
+    if (a->which != 0) {
+        if (a->critic.n_out != 1) return fail(IPLAN_EINVAL, "iplan_ac_saliency: the critic's head has one output (got %d)", a->critic.n_out);
+        if (!a->critic.params) return fail(IPLAN_EINVAL, "iplan_ac_saliency: critic parameters missing");
+        if (!a->h_critic) return fail(IPLAN_EINVAL, "iplan_ac_saliency: the critics' GRU state h_critic is missing");
+        any = any || a->values || a->entity_critic || a->input_grad_critic || a->act1_critic || a->act2_critic;
+    }
+    if (!any) return fail(IPLAN_EINVAL, "iplan_ac_saliency: no output was asked for");
+    if (!aligned16(a->act1_actor) || !aligned16(a->act2_actor) || !aligned16(a->act1_critic) || !aligned16(a->act2_critic) ||
+        !aligned16(a->packed_actor) || !aligned16(a->packed_critic) || (a->packed_s_net & 3))
+        return fail(IPLAN_EALIGN, "iplan_ac_saliency: act1, act2 and the packed operands must be 16-byte aligned");
+    return ac_saliency_launch(*a, (hipStream_t)stream);
 }

@@ -567,6 +567,114 @@ def policy_trace_args(actor_arena, critic_arena, which, spec, E, S, n_agents, hi
     return a, res, (spec, hidden0_actor, hidden0_critic, avail, actions_in, packed, gi)
 
 
+SALIENCY_OUTPUTS = ("y", "entity", "input_grad", "act")
+
+
+def saliency(actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
+             avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, want=("y", "entity"), packed=None,
+             out=None, lib=None):
+    """Input gradients of R_Actor (which=0) / R_Critic (1) / both (2) of every agent on E x S independent rows (iplan_ac_saliency; include/
+    iplan_hip.h: IplanAcSaliencyArgs): d log pi(a* | x) / d x and d V / d x with the row's GRU state GIVEN and held constant.  ``spec``:
+    the rows' features as for ``policy_trace`` (T = S, row (e, s) at physical row e * T_phys + s).  h_actor / h_critic [.., 64], avail
+    int32 [.., n_actions] and target int64 are addressed with their own (net, chain, step) strides; ``target`` None: ``target_all`` for
+    every row; -1 = the row's greedy action.  ``want``: "y" (logp, values, target_action [nA,E,S]), "entity" (entity_actor /
+    entity_critic [nA,E,S,N,n_src,2]: sum g x and sum |g| per entity and enabled source), "input_grad" (input_grad_* [nA,E,S,F], the
+    reference's column order), "act" (act1_* / act2_* [nA,E,S,64], the trunk's post-activation tiles).  ``out``: optional dict of
+    contiguous destinations.  ``packed``: Fc1Pack.get(spec) or None (same bits).  Everything the kernel will read is bounds-checked here,
+    on the host.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res, _keep = saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor, h_critic, h_strides, avail, avail_strides,
+                                  target, target_strides, target_all, n_actions, want, packed, out)
+    dev = (actor_arena if which != 1 else critic_arena).data.device
+    nets = n_agents * (2 if which == 2 else 1)
+    _launch("ac_saliency", lambda: lib.call("iplan_ac_saliency", a, L.current_stream(dev)),
+            work=2.0 * nets * E * S * L.AC_HIDDEN * (3 * spec.F + 14 * L.AC_HIDDEN))
+    return res
+
+
+def saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
+                  avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, want=("y", "entity"), packed=None,
+                  out=None):
+    """The descriptor of a ``saliency`` launch, its output tensors and the operands to keep alive until the launch has been queued,
+    checked but not launched: (IplanAcSaliencyArgs, dict, tuple)."""
+    assert which in (0, 1, 2) and E >= 1 and S >= 1 and n_agents >= 1, (which, E, S, n_agents)
+    want = tuple(want)
+    assert want and all(k in SALIENCY_OUTPUTS for k in want), want
+    arena0 = actor_arena if which != 1 else critic_arena
+    dev = arena0.data.device
+    M = L.AC_HIDDEN
+    a = L.AcSaliencyArgs()
+    a.n_agents, a.E, a.S, a.which, a.target_all = n_agents, E, S, which, target_all
+    a.act_tanh = int(bool(getattr(arena0, "act_tanh", False)))
+    if which == 2:
+        assert bool(getattr(actor_arena, "act_tanh", False)) == bool(getattr(critic_arena, "act_tanh", False)), \
+            "actor and critic of one launch must use the same trunk activation (args.use_ReLU)"
+    assert spec.T == S and spec.T_phys >= S, (spec.T, spec.T_phys, S)
+    spec.fill(a.feat)
+    last_row = (E - 1) * spec.T_phys + S - 1                         # the largest physical row
+    for t, w, s_net, s_row in spec.sources:
+        assert t.device == dev and min(s_net, s_row) >= 0
+        _inside(t, (n_agents - 1) * s_net + last_row * s_row + spec.N * w, "feature source")
+    if spec.last_action is not None and spec.n_actions > 0:
+        assert spec.last_action.device == dev and min(spec.la_strides) >= 0
+        _inside(spec.last_action, (n_agents - 1) * spec.la_strides[0] + last_row * spec.la_strides[1] + 1, "last_action")
+    n_src = sum(1 for s in spec.sources if s[1] > 0)
+    res = {}
+
+    def dest(k, shape, dtype=torch.float32):
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(*shape, dtype=dtype, device=dev)
+        assert t.shape == tuple(shape) and t.dtype == dtype and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
+        res[k] = t
+        return t.data_ptr()
+
+    def reach(strides, width):
+        assert len(strides) == 3 and min(strides) >= 0, strides
+        return (n_agents - 1) * strides[0] + (E - 1) * strides[1] + (S - 1) * strides[2] + width
+
+    for net, h, key in ((0, h_actor, "actor"), (1, h_critic, "critic")):
+        if which == 1 - net:
+            continue
+        assert h is not None and h.dtype == torch.float32 and h.device == dev, ("the GRU state of the " + key + "s is needed",)
+        _inside(h, reach(h_strides, M), "h_" + key)
+        setattr(a, "h_" + key, h.data_ptr())
+        if "entity" in want:
+            setattr(a, "entity_" + key, dest("entity_" + key, (n_agents, E, S, spec.N, n_src, 2)))
+        if "input_grad" in want:
+            setattr(a, "input_grad_" + key, dest("input_grad_" + key, (n_agents, E, S, spec.F)))
+        if "act" in want:
+            setattr(a, "act1_" + key, dest("act1_" + key, (n_agents, E, S, M)))
+            setattr(a, "act2_" + key, dest("act2_" + key, (n_agents, E, S, M)))
+    a.hs_net, a.hs_chain, a.hs_step = h_strides
+    if which != 1:
+        _fill_acnet(a.actor, actor_arena, L.ACTOR_PARAM_ORDER, n_actions)
+        if avail is not None:
+            assert avail.dtype == torch.int32 and avail.device == dev
+            _inside(avail, reach(avail_strides, n_actions), "avail")
+            a.avail = avail.data_ptr()
+            a.av_s_net, a.av_s_chain, a.av_s_step = avail_strides
+        if target is not None:
+            assert target.dtype == torch.int64 and target.device == dev
+            _inside(target, reach(target_strides, 1), "target")
+            a.target = target.data_ptr()
+            a.tg_s_net, a.tg_s_chain, a.tg_s_step = target_strides
+        if "y" in want:
+            a.logp = dest("logp", (n_agents, E, S))
+            a.target_out = dest("target_action", (n_agents, E, S), torch.int64)
+    if which != 0:
+        _fill_acnet(a.critic, critic_arena, L.CRITIC_PARAM_ORDER, 1)
+        if "y" in want:
+            a.values = dest("values", (n_agents, E, S))
+    if packed is not None:                                 # Fc1Pack.get(spec): the fragment part and gamma are all the kernel reads
+        pa, pc = packed
+        if which != 1:
+            a.packed_actor, a.packed_s_net = pa.data_ptr(), pa.stride(0)
+        if which != 0:
+            a.packed_critic, a.packed_s_net = pc.data_ptr(), pc.stride(0)
+    return a, res, (spec, h_actor, h_critic, avail, target, packed)
+
+
 def ppo_eval(logp, entropy, values, old_logp, adv, value_preds, returns, mask, T, rows=None, clip=0.2, huber_delta=10.0,
              value_loss_coef=1.0, flags=0, n_parts=0, want=(), out=None, lib=None):
     """The PPO statistics of recorded rows under the nets, forward only (iplan_ppo_eval; include/iplan_hip.h: IplanPpoEvalArgs).
