@@ -1031,6 +1031,40 @@ typedef struct {
 int iplan_ac_saliency(const IplanAcSaliencyArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Policy saliency through time (BPTT over the recurrent state): d y_s / d x_{s-k}, the sensitivity of the output of step s to the
+ * inputs of step s - k, for every slot (e, s) of E chains x S consecutive steps; one launch is ONE lag k for all slots, agents and
+ * selected nets.  `base` describes the rows exactly as for iplan_ac_saliency, with the state ENTERING step s of chain e at
+ * h + net*hs_net + e*hs_chain + s*hs_step -- the caller's self-consistent chain, h_s = GRU(trunk(x_s), h_{s-1}) before rnn.norm (what
+ * iplan_ac_trace's h_all_* holds, shifted by one step behind hidden0).  Slot r = e*S + s:
+ *   lag == 0   iplan_ac_saliency's arithmetic, bit for bit (head seed, target / avail handling, logp / values / target_out / act1 / act2
+ *              [n_agents, E*S, ..] as there), and additionally
+ *                carry = delta^(0) = d y_s / d h_{s-1} = z * d y / d h' + W_hh^T [dr | dz | r * dn]
+ *   lag k >= 1 the slot reads the input row, the last action and the entering state of step s - k, and takes seed = delta^(k-1) of the
+ *              SAME slot as d y_s / d h_{s-k} at the GRU output: no rnn.norm, head or softmax, nothing of logp / values / target_out /
+ *              act1 / act2 is written.  It writes the lag-k gradient and carry = delta^(k) = (d h_{s-k} / d h_{s-k-1})^T seed.
+ *              Slots with s < k write NOTHING.
+ * entity_* and input_grad_* carry a lag axis of n_lags entries: [n_agents, E*S, n_lags, N, n_src, 2] and [n_agents, E*S, n_lags, F];
+ * this launch writes entry `lag` of it.  seed_* / carry_*: 64 floats per slot at ptr + (net*E*S + r) * seed_s_row / carry_s_row; a
+ * slot reads its seed before it writes its carry and touches no other slot's, so seed and carry may be the same memory (in place) or
+ * two entries of one [.., n_lags, 64] buffer.  carry_* may be NULL only when lag + 1 == n_lags (nothing follows).
+ * Determinism and memory rules of iplan_ac_saliency: no atomics, no cross-row sums, a slot's results do not depend on its lane, tile or
+ * workgroup; parameter, gradient and batch memory is only read.  0 <= lag < n_lags <= S; seed, carry, act1 / act2 and the packed
+ * operands 16-byte aligned, seed_s_row and carry_s_row multiples of 4.
+ */
+typedef struct {
+    IplanAcSaliencyArgs base;
+    int32_t lag, n_lags;
+    const float* seed_actor;    /* lag >= 1: delta^(lag-1) of the nets `base.which` selects                   */
+    const float* seed_critic;
+    int64_t seed_s_row;
+    float* carry_actor;         /* delta^(lag)                                                             */
+    float* carry_critic;
+    int64_t carry_s_row;
+} IplanAcSaliencyLagArgs;
+
+int iplan_ac_saliency_lag(const IplanAcSaliencyLagArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Three-layer perceptron of the FC behaviour ablation (nova/behavior_FC_net.py:6-37, Encoder_3FC / Decoder_3FC):
  *   out = [softmax] (W3 tanh(W2 tanh(W1 x + b1) + b2) + b3)   for n_nets stacked nets, rows per net.
  * off[0..5] = linear_1.weight [H,K0], linear_1.bias, linear_2.weight [H,H], linear_2.bias, out.weight [O,H], out.bias.

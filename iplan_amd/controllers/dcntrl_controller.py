@@ -259,7 +259,8 @@ class DcntrlMAC:
         Device tensors in -> device tensors out, numpy in -> numpy out.  Draws from no generator; parameters, gradient entries,
         optimiser state, ``hidden_states`` and the batch are not touched; the packed fc1 operands are brought up to date exactly as
         ``policy_trace`` does it (the values any later launch would pack), the kernel only reads them.  Not covered: layer_N /
-        recurrent_N other than 1, saliency through the GAT or the behaviour encoder back to the raw history, BPTT."""
+        recurrent_N other than 1, saliency through the GAT or the behaviour encoder back to the raw history; through time:
+        ``saliency_trace``."""
         a = self.args
         if a.layer_N != 1 or a.recurrent_N != 1:
             raise NotImplementedError("saliency covers layer_N = recurrent_N = 1 only")
@@ -338,6 +339,142 @@ class DcntrlMAC:
                     out[net + "_" + k] = res[k + "_" + net].permute(1, 2, 0, 3)
         if one:
             out = {k: (v if k == "sources" else v[:, 0]) for k, v in out.items()}
+        return {k: (v if k == "sources" else v.cpu().numpy()) for k, v in out.items()} if as_np else out
+
+    def saliency_trace(self, batch, lags, target="recorded", which="both", hidden0=None, steps=None, want=("entity",)):
+        """How far back does this policy look, and at whom?  ``saliency`` through time: the total derivative of the output of step s,
+        y_s = log pi(a*_s | x_s, h_{s-1}) of the actors / V(x_s, h_{s-1}) of the critics, with respect to the INPUT row of step s - k,
+        g_s^(k) = d y_s / d x_{s-k}, k = 0 .. ``lags``, through the recurrent state (BPTT over the GRU chain, truncated at ``lags``).
+        The chain is the one ``policy_trace`` walks: h_s = GRU(trunk(x_s), h_{s-1}) with THESE nets' own states (the GRU output before
+        rnn.norm), from ``hidden0`` -- None = the batch's ``rnn_states_actors[:, t0]`` / ``rnn_states_critics[:, t0]``, "zeros", or a
+        pair of [E, nA, M] tensors -- traced first (ops.policy_trace); ``lags + 1`` launches follow (ops.saliency_lag), lag k seeded
+        with d y_s / d h_{s-k}, the carry lag k - 1 left.  ``batch``, ``target`` and ``which`` as for ``saliency``.  ``steps``: None =
+        every step, or a slice with step 1: the inspected window [t0, t0 + S); the chain starts at t0 and lags reaching before it do
+        not exist.  ``lags``: an int in [0, S - 1]; S - 1 is full BPTT over the window.  Anything else raises ValueError.
+        Returns a dict:
+          actor_gxi, actor_gl1, critic_gxi, critic_gl1 [E, S, K+1, nA, N, n_src]  entry [e, s, k]: what the inputs of step s - k
+                                    contribute to the output of step s (sum g x and sum |g| per entity and source); exactly 0 where s < k
+          lag_valid [S, K+1] bool   s >= k
+          actor_carry_l2, critic_carry_l2 [E, S, K+1, nA]  the 2-norm of d y_s / d h_{s-k-1}: what still flows into the state beyond lag k
+          actor_lag_l1, critic_lag_l1 [nA, K+1] float64  the mean over e and s >= k, with weight ``batch["filled"][e, s]``, of the row's
+                                    sum over entities and sources of gl1 (0 where the weights sum to 0); formed on the device in
+                                    float64, in environment order, from the per-row outputs: the "how far back" curve
+          logp, values, target_action [E, S, nA]; sources   as ``saliency``
+          h_actor, h_critic [E, S, nA, M]  the traced states (after every step)
+          actor_input_grad, critic_input_grad [E, S, K+1, nA, F]  with "input_grad" in ``want``
+          actor_act1, actor_act2, critic_act1, critic_act2 [E, S, nA, M]  with "act" in ``want`` (tests)
+          actor_carry, critic_carry [E, S, K+1, nA, M]  with "carry" in ``want``: d y_s / d h_{s-k-1} itself
+        Device tensors in -> device tensors out, numpy in -> numpy out.  Draws from no generator; parameters, gradient entries,
+        optimiser state, ``hidden_states`` and the batch are not touched.  Not covered: layer_N / recurrent_N other than 1, saliency
+        through the GAT or the behaviour encoder back to the raw history."""
+        a = self.args
+        if a.layer_N != 1 or a.recurrent_N != 1:
+            raise NotImplementedError("saliency_trace covers layer_N = recurrent_N = 1 only")
+        want = tuple(want)
+        assert all(k in ("entity", "input_grad", "act", "carry") for k in want), want
+        nA, N, M = self.n_agents, a.max_vehicle_num, a.rnn_hidden_dim
+        as_np = isinstance(batch["history"], np.ndarray)
+        T1 = batch["history"].shape[1]
+        if steps is None:
+            t0, S = 0, T1
+        else:
+            if not isinstance(steps, slice):
+                raise ValueError("saliency_trace: steps is None or a slice with step 1")
+            t0, t1, stride = steps.indices(T1)
+            if stride != 1 or t1 - t0 < 1:
+                raise ValueError("saliency_trace: steps is a non-empty slice with step 1")
+            S = t1 - t0
+        if isinstance(lags, bool) or not isinstance(lags, (int, np.integer)) or not 0 <= lags < S:
+            raise ValueError(f"saliency_trace: lags={lags!r} is not an int in [0, {S - 1}]")
+        K1 = int(lags) + 1
+        sl = slice(t0, t0 + S)
+
+        def dev(t, dtype=None):
+            return self._dev(th.as_tensor(t) if isinstance(t, np.ndarray) else t, dtype)
+
+        def field(key, dtype=None):
+            """[E, T1, ...] on the device, rows addressable as e * T1 + t (a copy only when the batch's layout is not that)"""
+            t = dev(batch[key], dtype)
+            return t if t.stride(0) == t.shape[1] * t.stride(1) and t[0, 0].is_contiguous() else t.contiguous()
+
+        # 1: the chain from hidden0, and the state entering every step: cat(hidden0, h[:, :-1])
+        w = {"actor": 0, "critic": 1, "both": 2}[which]
+        tr, _, _ = self._trace(batch, t0, S, hidden0, which, (), True)
+        E = tr["h_last_actor" if w != 1 else "h_last_critic"].shape[1]
+        enter = {}
+        for k, (net, on) in enumerate((("actor", w != 1), ("critic", w != 0))):
+            if not on:
+                continue
+            if isinstance(hidden0, str):
+                h0 = th.zeros(nA, E, 1, M, dtype=th.float32, device=self.device)
+            elif hidden0 is None:
+                h0 = field("rnn_states_" + net + "s", th.float32)[:, t0].permute(1, 0, 2).unsqueeze(2)
+            else:
+                h0 = dev(hidden0[k], th.float32).permute(1, 0, 2).unsqueeze(2)
+            enter[net] = th.cat([h0, tr["h_" + net][:, :, :-1]], 2)                                # [nA, E, S, M], contiguous
+        # 2: the rows, as saliency() describes them
+        hist = field("history", th.float32)
+        sources = []
+        for key, wd in self._widths():
+            view = (hist if key == "history" else field(key, th.float32))[:, sl]                  # [E, S, nA, N, w]
+            sources.append((view, wd, view.stride(2), view.stride(1)))
+        acts = field("actions")[..., 0]                                                           # [E, T1, nA] int64
+        last, la_strides = None, (0, 0)
+        if a.obs_last_action:
+            last = th.cat([th.full_like(acts[:, :1], -1), acts[:, :-1]], 1)[:, sl]                # the action of t - 1; none at t = 0
+            la_strides = (last.stride(2), last.stride(1))
+        spec = ops.AcFeatureSpec(N, sources, n_actions=a.n_actions if a.obs_last_action else 0, last_action=last, la_strides=la_strides,
+                                 n_id=nA if a.obs_agent_id else 0, T=S, T_phys=T1)
+        assert spec.F == self.input_shape, (spec.F, self.input_shape)
+        avail = field("avail_actions")
+        if avail.dtype != th.int32:
+            avail = avail.to(th.int32)
+        avail = avail[:, sl]
+        tgt = None
+        if isinstance(target, str):
+            assert target in ("recorded", "greedy"), target
+            if target == "recorded":
+                tgt = acts[:, sl]
+        else:
+            tgt = dev(target, th.int64)
+            assert tgt.shape == (E, S, nA), (tgt.shape, (E, S, nA))
+        esn = lambda t: (t.stride(2), t.stride(0), t.stride(1))                                   # noqa: E731  (net, chain, step)
+        any_h = enter["actor" if w != 1 else "critic"]
+        # 3: lags + 1 launches
+        res = ops.saliency_lag(self.actor_arena, self.critic_arena, w, spec, E, S, nA, K1 - 1, h_actor=enter.get("actor"),
+                               h_critic=enter.get("critic"), h_strides=(any_h.stride(0), any_h.stride(1), any_h.stride(2)), avail=avail,
+                               avail_strides=esn(avail), target=tgt, target_strides=esn(tgt) if tgt is not None else (0, 0, 0),
+                               target_all=-1, n_actions=a.n_actions, want=("y", "entity") + tuple(k for k in want if k in ("input_grad", "act")),
+                               packed=self.fc1_pack.get(spec))
+        lag_valid = th.arange(S, device=self.device)[:, None] >= th.arange(K1, device=self.device)[None, :]        # [S, K+1]
+        out = {"sources": tuple(k for k, _ in self._widths()), "lag_valid": lag_valid}
+        for k in ("logp", "values", "target_action"):
+            if k in res:
+                out[k] = res[k].permute(1, 2, 0)
+        filled = dev(batch["filled"]).reshape(-1, T1)[:, sl].to(th.float64)                      # [E, S]
+        for net in enter:
+            out["h_" + net] = tr["h_" + net].permute(1, 2, 0, 3)
+            ent = res["entity_" + net]                                                            # [nA, E, S, K+1, N, n_src, 2]
+            if "entity" in want:
+                pe = ent.permute(1, 2, 3, 0, 4, 5, 6)
+                out[net + "_gxi"], out[net + "_gl1"] = pe[..., 0], pe[..., 1]
+            carry = res["carry_" + net]                                                           # [nA, E, S, K+1, M]; 0 where s < k
+            out[net + "_carry_l2"] = carry.to(th.float64).pow(2).sum(-1).sqrt().to(th.float32).permute(1, 2, 3, 0)
+            if "carry" in want:
+                out[net + "_carry"] = carry.permute(1, 2, 3, 0, 4)
+            row = ent[..., 1].to(th.float64).sum((-1, -2))                                        # [nA, E, S, K+1]
+            wt = filled[:, :, None] * lag_valid                                                   # [E, S, K+1]
+            per_env = th.cat([(row * wt).sum(2), wt.sum(1)[None]])                                # [nA + 1, E, K+1]: weighted sums | weights
+            tot = th.zeros(nA + 1, K1, dtype=th.float64, device=self.device)
+            for e in range(E):                                                                    # environment order
+                tot += per_env[:, e]
+            num, den = tot[:nA], tot[nA]
+            out[net + "_lag_l1"] = th.where(den > 0, num / den.clamp_min(1e-300), th.zeros_like(num))
+            if "input_grad" in want:
+                out[net + "_input_grad"] = res["input_grad_" + net].permute(1, 2, 3, 0, 4)
+            if "act" in want:
+                for k in ("act1", "act2"):
+                    out[net + "_" + k] = res[k + "_" + net].permute(1, 2, 0, 3)
         return {k: (v if k == "sources" else v.cpu().numpy()) for k, v in out.items()} if as_np else out
 
     def get_value_ippo(self, agent_id, obs, rnn_states_critic):

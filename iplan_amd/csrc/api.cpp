@@ -1,5 +1,5 @@
 // C-ABI bookkeeping: version + thread-local error string; the argument checks of iplan_ppo_eval (kernels: ppo_eval.hip) and of
-// iplan_ac_saliency (kernel: policy_saliency.hip).
+// iplan_ac_saliency (kernel: policy_saliency.hip) and of iplan_ac_saliency_lag (kernels: policy_saliency_lag.hip).
 #include <cstring>
 
 #include "api_util.h"
@@ -11,6 +11,7 @@ char* error_buffer() {
 }
 int ppo_eval_launch(const IplanPpoEvalArgs& a, hipStream_t stream);   // ppo_eval.hip
 int ac_saliency_launch(const IplanAcSaliencyArgs& a, hipStream_t stream);   // policy_saliency.hip
+int ac_saliency_lag_launch(const IplanAcSaliencyLagArgs& a, hipStream_t stream);   // policy_saliency_lag.hip
 }  // namespace iplan
 
 extern "C" const char* iplan_last_error(void) { return iplan::error_buffer(); }
@@ -23,7 +24,7 @@ extern "C" size_t iplan_sizeof(const char* name) {
     IPLAN_SZ(IplanAcFeatures) IPLAN_SZ(IplanAcFwdArgs) IPLAN_SZ(IplanAcBwdArgs) IPLAN_SZ(IplanAdamArgs) IPLAN_SZ(IplanWgradProblem)
     IPLAN_SZ(IplanWgradArgs) IPLAN_SZ(IplanPpoPrepareArgs) IPLAN_SZ(IplanPpoLossArgs) IPLAN_SZ(IplanPdecArgs) IPLAN_SZ(IplanBehArgs) IPLAN_SZ(IplanMlp3Args) IPLAN_SZ(IplanAdvNormArgs) IPLAN_SZ(IplanSeq2SeqArgs) IPLAN_SZ(IplanAcPackArgs) IPLAN_SZ(IplanP2pArgs) IPLAN_SZ(IplanIpcHandle) IPLAN_SZ(IplanAcXhatArgs) IPLAN_SZ(IplanAcFc1SplitArgs) IPLAN_SZ(IplanObsHistArgs) IPLAN_SZ(IplanSeq2SeqBwdArgs)
     IPLAN_SZ(IplanPredictArgs) IPLAN_SZ(IplanBehEvalArgs) IPLAN_SZ(IplanGatTraceArgs) IPLAN_SZ(IplanAcTraceArgs) IPLAN_SZ(IplanPpoEvalArgs)
-    IPLAN_SZ(IplanAcSaliencyArgs)
+    IPLAN_SZ(IplanAcSaliencyArgs) IPLAN_SZ(IplanAcSaliencyLagArgs)
 #undef IPLAN_SZ
     return 0;
 }
@@ -54,9 +55,9 @@ extern "C" int iplan_ppo_eval(const IplanPpoEvalArgs* a, iplan_stream_t stream) 
     return ppo_eval_launch(*a, (hipStream_t)stream);
 }
 
-extern "C" int iplan_ac_saliency(const IplanAcSaliencyArgs* a, iplan_stream_t stream) {
+// the checks iplan_ac_saliency and iplan_ac_saliency_lag share; `outputs`: at least one output must be asked for
+static int saliency_check(const IplanAcSaliencyArgs* a, bool outputs) {
     using namespace iplan;
-    if (!a) return fail(IPLAN_EINVAL, "iplan_ac_saliency: null args");
     if (a->which < 0 || a->which > 2 || a->n_agents < 1) return fail(IPLAN_EINVAL, "iplan_ac_saliency: bad which=%d / n_agents=%d", a->which, a->n_agents);
     if (a->E < 1 || a->S < 1) return fail(IPLAN_EINVAL, "iplan_ac_saliency: E=%d x S=%d rows, at least one row is needed", a->E, a->S);
     if ((int64_t)a->E * a->S > 0x7fffffff / 16) return fail(IPLAN_EINVAL, "iplan_ac_saliency: E * S = %lld rows are too many", (long long)a->E * a->S);
@@ -82,9 +83,44 @@ extern "C" int iplan_ac_saliency(const IplanAcSaliencyArgs* a, iplan_stream_t st
         if (!a->h_critic) return fail(IPLAN_EINVAL, "iplan_ac_saliency: the critics' GRU state h_critic is missing");
         any = any || a->values || a->entity_critic || a->input_grad_critic || a->act1_critic || a->act2_critic;
     }
-    if (!any) return fail(IPLAN_EINVAL, "iplan_ac_saliency: no output was asked for");
+    if (outputs && !any) return fail(IPLAN_EINVAL, "iplan_ac_saliency: no output was asked for");
     if (!aligned16(a->act1_actor) || !aligned16(a->act2_actor) || !aligned16(a->act1_critic) || !aligned16(a->act2_critic) ||
         !aligned16(a->packed_actor) || !aligned16(a->packed_critic) || (a->packed_s_net & 3))
         return fail(IPLAN_EALIGN, "iplan_ac_saliency: act1, act2 and the packed operands must be 16-byte aligned");
+    return IPLAN_OK;
+}
+
+extern "C" int iplan_ac_saliency(const IplanAcSaliencyArgs* a, iplan_stream_t stream) {
+    using namespace iplan;
+    if (!a) return fail(IPLAN_EINVAL, "iplan_ac_saliency: null args");
+    if (const int rc = saliency_check(a, true)) return rc;
     return ac_saliency_launch(*a, (hipStream_t)stream);
+}
+
+extern "C" int iplan_ac_saliency_lag(const IplanAcSaliencyLagArgs* x, iplan_stream_t stream) {
+    using namespace iplan;
+    if (!x) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: null args");
+    const IplanAcSaliencyArgs* a = &x->base;
+    if (const int rc = saliency_check(a, false)) return rc;                  // (the row description: iplan_ac_saliency's rules)
+    if (x->n_lags < 1 || x->n_lags > a->S) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: n_lags=%d outside [1, S=%d]", x->n_lags, a->S);
+    if (x->lag < 0 || x->lag >= x->n_lags) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: lag=%d outside [0, n_lags=%d)", x->lag, x->n_lags);
+    if (x->seed_s_row < 0 || x->carry_s_row < 0) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: negative seed / carry stride");
+    bool any = false;
+    for (int net = 0; net < 2; ++net) {
+        if (a->which == 1 - net) continue;
+        const float* seed = net ? x->seed_critic : x->seed_actor;
+        const float* carry = net ? x->carry_critic : x->carry_actor;
+        const char* who = net ? "critics" : "actors";
+        if (x->lag >= 1 && !seed) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: lag=%d needs the %s' seed (the carry of lag %d)", x->lag, who, x->lag - 1);
+        if (x->lag + 1 < x->n_lags && !carry) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: lag %d follows, the %s' carry is needed", x->lag + 1, who);
+        if (x->lag >= 1 && seed && x->seed_s_row < IPLAN_AC_HIDDEN) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: seed_s_row=%lld < 64", (long long)x->seed_s_row);
+        if (carry && x->carry_s_row < IPLAN_AC_HIDDEN) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: carry_s_row=%lld < 64", (long long)x->carry_s_row);
+        any = any || carry || (net ? a->entity_critic || a->input_grad_critic : a->entity_actor || a->input_grad_actor);
+        if (x->lag == 0) any = any || (net ? a->values || a->act1_critic || a->act2_critic : a->logp || a->target_out || a->act1_actor || a->act2_actor);
+    }
+    if (!any) return fail(IPLAN_EINVAL, "iplan_ac_saliency_lag: no output of lag %d was asked for", x->lag);
+    if (!aligned16(x->seed_actor) || !aligned16(x->seed_critic) || !aligned16(x->carry_actor) || !aligned16(x->carry_critic) || (x->seed_s_row & 3) ||
+        (x->carry_s_row & 3))
+        return fail(IPLAN_EALIGN, "iplan_ac_saliency_lag: seed and carry must be 16-byte aligned, their row strides multiples of 4");
+    return ac_saliency_lag_launch(*x, (hipStream_t)stream);
 }

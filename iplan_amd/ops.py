@@ -675,6 +675,79 @@ def saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_acto
     return a, res, (spec, h_actor, h_critic, avail, target, packed)
 
 
+def saliency_lag(actor_arena, critic_arena, which, spec, E, S, n_agents, lags, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
+                 avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, want=("y", "entity"), packed=None,
+                 out=None, lib=None):
+    """Input gradients THROUGH TIME of R_Actor (which=0) / R_Critic (1) / both (2) of every agent on the slots (e, s) of E chains x S
+    consecutive steps (iplan_ac_saliency_lag; include/iplan_hip.h: IplanAcSaliencyLagArgs): d y_s / d x_{s-k} for k = 0 .. ``lags``, in
+    ``lags + 1`` launches, lag k seeded with the carry d y_s / d h_{s-k} lag k - 1 left.  Arguments as for ``saliency``, except that
+    h_actor / h_critic hold the state ENTERING each step of a self-consistent chain (the caller's, from ``policy_trace``).  Results as
+    ``saliency``'s with a lag axis behind the step axis of entity_* [nA,E,S,lags+1,N,n_src,2] and input_grad_* [nA,E,S,lags+1,F], and
+    carry_actor / carry_critic [nA,E,S,lags+1,64], the carry after every lag; entries with s < k are NOT written (``out`` decides what
+    they hold; fresh buffers are zeroed).  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    launches, res, _keep = saliency_lag_args(actor_arena, critic_arena, which, spec, E, S, n_agents, lags, h_actor, h_critic, h_strides, avail,
+                                             avail_strides, target, target_strides, target_all, n_actions, want, packed, out)
+    dev = (actor_arena if which != 1 else critic_arena).data.device
+    nets = n_agents * (2 if which == 2 else 1)
+    for a in launches:
+        _launch("ac_saliency_lag", lambda: lib.call("iplan_ac_saliency_lag", a, L.current_stream(dev)),
+                work=2.0 * nets * E * (S - a.lag) * L.AC_HIDDEN * (3 * spec.F + 17 * L.AC_HIDDEN))
+    return res
+
+
+def saliency_lag_args(actor_arena, critic_arena, which, spec, E, S, n_agents, lags, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
+                      avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, want=("y", "entity"),
+                      packed=None, out=None):
+    """The descriptors of a ``saliency_lag`` call, one per lag in launch order, its output tensors and the operands to keep alive until
+    the launches have been queued, checked but not launched: ([IplanAcSaliencyLagArgs], dict, tuple)."""
+    assert isinstance(lags, int) and 0 <= lags < S, (lags, S)
+    K1 = lags + 1
+    M = L.AC_HIDDEN
+    dev = (actor_arena if which != 1 else critic_arena).data.device
+    n_src = sum(1 for s in spec.sources if s[1] > 0)
+    nets = [k for k, on in (("actor", which != 1), ("critic", which != 0)) if on]
+    shapes = {}
+    for key in nets:
+        shapes["carry_" + key] = (n_agents, E, S, K1, M)
+        if "entity" in want:
+            shapes["entity_" + key] = (n_agents, E, S, K1, spec.N, n_src, 2)
+        if "input_grad" in want:
+            shapes["input_grad_" + key] = (n_agents, E, S, K1, spec.F)
+    lagged = {}
+    for k, shape in shapes.items():
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.zeros(*shape, dtype=torch.float32, device=dev)
+        assert t.shape == shape and t.dtype == torch.float32 and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
+        lagged[k] = t
+    # the row description, the checks and the lag-0-only outputs are saliency's; the lagged outputs are set below
+    base, res, keep = saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor, h_critic, h_strides, avail, avail_strides,
+                                    target, target_strides, target_all, n_actions, tuple(k for k in want if k in ("y", "act")) or ("y",), packed,
+                                    out)
+    if "y" not in want:
+        for k in ("logp", "values", "target_action"):
+            res.pop(k, None)
+        base.logp = base.values = base.target_out = None
+    res.update(lagged)
+    launches = []
+    for lag in range(K1):
+        x = L.AcSaliencyLagArgs()
+        C.memmove(C.byref(x.base), C.byref(base), C.sizeof(base))
+        x.lag, x.n_lags = lag, K1
+        x.seed_s_row = x.carry_s_row = K1 * M
+        for key in nets:
+            for k in ("entity_", "input_grad_"):
+                if k + key in lagged:
+                    setattr(x.base, k + key, lagged[k + key].data_ptr())
+            carry = lagged["carry_" + key]
+            setattr(x, "carry_" + key, carry.data_ptr() + 4 * M * lag)
+            if lag:
+                setattr(x, "seed_" + key, carry.data_ptr() + 4 * M * (lag - 1))
+        launches.append(x)
+    return launches, res, keep + (lagged,)
+
+
 def ppo_eval(logp, entropy, values, old_logp, adv, value_preds, returns, mask, T, rows=None, clip=0.2, huber_delta=10.0,
              value_loss_coef=1.0, flags=0, n_parts=0, want=(), out=None, lib=None):
     """The PPO statistics of recorded rows under the nets, forward only (iplan_ppo_eval; include/iplan_hip.h: IplanPpoEvalArgs).
