@@ -778,9 +778,13 @@ __device__ __forceinline__ void ac_fwd_body(const IplanAcFwdArgs& a, const AcGri
     float se = 0.f;
     for (int q = 0; q < 4; ++q) { e[q] = (4 * g + q < n_out) ? expf(x[q] - m) : 0.f; se += e[q]; }
     se = group_sum(se);
-    const float lse = m + logf(se);
+    // A row with NO available action: every logit is the mask value, m = -1e10 swallows log(se) in fp32 and x - (m + log se) is 0
+    // where log_softmax gives -log(n_out).  That row subtracts the maximum first; every other row keeps x - (m + log se) and its bits.
+    const float lgse = logf(se);
+    const float lse = m + lgse;
+    const bool none_avail = m <= -1e10f;
     f32x4 lp, pb;
-    for (int q = 0; q < 4; ++q) { lp[q] = x[q] - lse; pb[q] = e[q] / se; }
+    for (int q = 0; q < 4; ++q) { lp[q] = none_avail ? (x[q] - m) - lgse : x[q] - lse; pb[q] = e[q] / se; }
     int action = 0;
     if (a.mode == 2) {
         action = valid ? (int)a.actions_in[(int64_t)net * a.act_s_net + pr * a.act_s_row] : 0;

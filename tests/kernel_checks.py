@@ -511,7 +511,7 @@ def check_mlp3(device, K0, H, O, rows, softmax, n_nets=2):
 # ------------------------------------------------------------------------------------------------ actor / critic backward
 def check_ac_backward(device, n_agents=2, max_vehicle_num=4, E=4, T=5):
     """ops.ac_forward (evaluation mode, saved activations) + ops.ac_backward against fp64 autograd of the oracle: log-probs,
-    entropies, values, and every actor / critic parameter gradient at 1e-5 of the tensor's maximum"""
+    entropies, values, the new GRU states, and every actor / critic parameter gradient at 1e-5 of the tensor's maximum"""
     from iplan_amd import synth
     from iplan_amd.config import default_args
     from iplan_amd.controllers.dcntrl_controller import DcntrlMAC
@@ -536,7 +536,7 @@ def check_ac_backward(device, n_agents=2, max_vehicle_num=4, E=4, T=5):
     out = ops.ac_forward(mac.actor_arena, mac.critic_arena, 2, spec, rows, nA, h_actor=ha, h_critic=hc,
                          h_strides=(ha.stride(2), ha.stride(1)), avail=avail, avail_strides=(avail.stride(2), avail.stride(1)),
                          mode=2, actions_in=actions, act_strides=(actions.stride(2), actions.stride(1)), n_actions=5,
-                         ksplit=1, save=True, want_entropy=True, want_h=False)
+                         ksplit=1, save=True, want_entropy=True, want_h=True)
     gen = torch.Generator().manual_seed(17)
     g_logp, g_v = torch.randn(nA, rows, generator=gen), torch.randn(nA, rows, generator=gen)
     g_ent = -0.01 / rows
@@ -552,11 +552,12 @@ def check_ac_backward(device, n_agents=2, max_vehicle_num=4, E=4, T=5):
                                  f["actions_onehot"][:, :, i], nA)[:, :-1].reshape(rows, -1).double()
         lp, _ = O.actor_evaluate(ap, x, ha[:, :-1, i].reshape(rows, -1).double(), actions[:, :-1, i].reshape(rows, 1),
                                  avail[:, :-1, i].reshape(rows, -1))
-        logits, _ = O.actor_logits(ap, x, ha[:, :-1, i].reshape(rows, -1).double(), avail[:, :-1, i].reshape(rows, -1))
+        logits, ha_new = O.actor_logits(ap, x, ha[:, :-1, i].reshape(rows, -1).double(), avail[:, :-1, i].reshape(rows, -1))
         la = torch.log_softmax(logits, -1)
         ent_rows = -(la.exp() * la).sum(-1)
-        v, _ = O.critic_value(cp, x, hc[:, :-1, i].reshape(rows, -1).double())
-        for key, got, ref in (("logp", out["logp"][i], lp[:, 0]), ("entropy", out["entropy"][i], ent_rows), ("values", out["values"][i], v[:, 0])):
+        v, hc_new = O.critic_value(cp, x, hc[:, :-1, i].reshape(rows, -1).double())
+        for key, got, ref in (("logp", out["logp"][i], lp[:, 0]), ("entropy", out["entropy"][i], ent_rows), ("values", out["values"][i], v[:, 0]),
+                              ("h_actor", out["h_actor"][i], ha_new), ("h_critic", out["h_critic"][i], hc_new)):
             e = rel(got, ref.detach())
             _worse(worst, key, e)
             assert e < 1e-5, (key, i, e)
