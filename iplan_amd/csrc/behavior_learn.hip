@@ -944,7 +944,10 @@ __global__ __launch_bounds__(256) void beh_enc_bwd_kernel(IplanBehArgs a) {
         // ---- latent update + head backward (dlat = d(loss)/d(latent_{j+1}) on entry)
         f32x4 dlog[1], hL[ET];
         {
-            const f32x4 nl = zero_unless(ok, win.nl);
+            // Z = 1: the softmax is the constant 1 and its Jacobian exactly 0, but dnew - s below is not -- contracted to
+            // fma(cn, dlat, -s) it leaves the rounding error of the product s was summed from, 1e-10 of the decoder's gradients in
+            // every encoder tensor where fp64 autograd gives 0.  The head is switched off there; Z > 1 keeps its arithmetic.
+            const f32x4 nl = zero_unless(ok && a.Z > 1, win.nl);
             float s = 0.f;
             f32x4 dnew;
             for (int q = 0; q < 4; ++q) { dnew[q] = cn * dlat[q]; s = fmaf(nl[q], dnew[q], s); }
