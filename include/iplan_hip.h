@@ -865,6 +865,62 @@ typedef struct {
 int iplan_beh_eval(const IplanBehEvalArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Intent saliency: the derivative of the intent latent with respect to the RAW history, by BPTT through the encoder chain
+ * iplan_beh_eval walks (no decoder is involved):
+ *   he_{-1} = 0, lat_{-1} = 0;  window j < J = T - 1 - L:  h = he_{j-1};  t < L:  s = j-L+1+t, x~ = x_s (0 where s < 0),
+ *   u = ReLU(W_lin x~ + b_lin), h = GRU32(u, h);  he_j = h, p_j = softmax(W_out he_j + b_out), lat_j = (1 - coef) lat_{j-1} + coef p_j
+ * For every chain (net, row = e*N + i) and every target window j = windows[w], w < nW (sorted, distinct, in [0, J)):
+ *   y = <v, lat_j>,  v = seed[net, row, w, :] or, with seed == NULL, the one-hot of seed_index (>= 0) or of the chain's own
+ *   argmax_z lat_j (seed_index == -1; lowest index on ties);
+ *   windows j - Kj .. j are unrolled, Kj = min(K, j); he_{j-Kj-1} and lat_{j-Kj-1} are constants (both 0 when Kj == j: the result is
+ *   then the exact total derivative);   G[r, c] = d y / d x_{j-r, c},  r < R = K + L  (a step read by several windows: the sum).
+ * G[r] is 0.0 where j - r < 0 (zero padding) and where r > Kj + L - 1.  rows = E * N; 1 <= d <= 16, 1 <= Z <= 16;
+ * 1 <= L <= IPLAN_ENC_SAL_MAX_L; J >= 1; K >= 0; nW >= 1; n_nets <= IPLAN_MAX_NETS.  Outputs, each optional (at least one is asked for):
+ *   grad         [n_nets, rows, nW, R, d]   G
+ *   step_l1      [n_nets, rows, nW, R]      sum_c |G[r, c]|
+ *   step_gxi     [n_nets, rows, nW, R]      sum_c G[r, c] x_{j-r, c}
+ *   feature_l1   [n_nets, rows, nW, d]      sum_r |G[r, c]|, r ascending
+ *   carry_l2     [n_nets, rows, nW]         || d y / d he_{j-Kj-1} ||_2; 0.0 where Kj == j
+ *   latent       [n_nets, rows, nW, Z]      lat_j
+ *   target_index [n_nets, rows, nW] int32   the component the one-hot v selects (seed == NULL only)
+ *   active       [n_nets, rows, nW, K+1, L] uint32: bit m = unit m of the input Linear has u > 0 at window j - k, position t, as the
+ *                backward pass recomputed it; 0 where k > Kj
+ * Two passes: a forward walk over windows 0 .. max(windows) that keeps he_j and the argmax in `scratch`, then one wave per (16-chain
+ * tile, target window) that walks windows j .. j - Kj backwards, restarting each from he_{w-1} and recomputing the gates; a step's
+ * gradient is complete once the window that ends at it has been walked, so at most L rows are pending at a time (in LDS).
+ * scratch: at least 32 * n_nets * rows * (max(windows) + 1) + n_nets * rows * nW floats, 16-byte aligned -- it does not grow with K.
+ * No atomics, no cross-chain sums: a slot's bits do not depend on its lane, tile, workgroup or on the other entries of `windows`;
+ * two launches give the same bits; padding lanes of a ragged last tile write nothing; parameters and history are only read.
+ * With Z == 1 every gradient and the carry are exactly 0.0 (the softmax is constant).
+ */
+#define IPLAN_ENC_SAL_MAX_L 30      /* the window's L hidden states and L pending rows of one wave beside the weights in LDS */
+typedef struct {
+    int32_t n_nets, E, N, T, L, d, Z, K, nW;
+    const float* hist;          /* x(net,e,t,i,c) = hist[net*h_s_net + e*h_s_e + t*h_s_t + i*d + c]      */
+    int64_t h_s_net, h_s_e, h_s_t;
+    const int32_t* windows;     /* [nW] device memory                                                    */
+    const int32_t* windows_host;/* the same values in host memory (argument checks, grid size)           */
+    const float* seed;          /* [n_nets, rows, nW, Z] or NULL                                         */
+    int32_t seed_index;         /* seed == NULL: -1 = argmax of lat_j, >= 0 = that component             */
+    float coef;                 /* soft_update_coef                                                      */
+    const float* enc_params;    /* encoder arena, IPLAN_ENC_* offsets                                    */
+    int64_t enc_s_net;
+    int64_t enc_off[IPLAN_ENC_NPARAM];
+    float* scratch;
+    int64_t scratch_floats;
+    float* grad;
+    float* step_l1;
+    float* step_gxi;
+    float* feature_l1;
+    float* carry_l2;
+    float* latent;
+    int32_t* target_index;
+    uint32_t* active;
+} IplanEncSaliencyArgs;
+
+int iplan_enc_saliency(const IplanEncSaliencyArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Attention inspection: GAT_Net.forward walked over S >= 1 consecutive steps in one launch, forward only,
  *   h_s = GAT([src0_s || src1_s], h_{s-1}),   s = 0 .. S-1,   h_{-1} = hidden0 (NULL: zeros),
  * one workgroup per (net, env) scene; a step's arithmetic is the inference form of iplan_gat_fwd (nothing saved), so the

@@ -387,6 +387,159 @@ class Behavior_policy:
         lat = out["latent"].reshape(nA, E, N, J, self.latent_dim).permute(1, 3, 0, 2, 4)
         return lat.cpu().numpy() if as_np else lat
 
+    def latent_saliency(self, history, windows=None, lags=None, target="argmax", want=("step",), presence_col=0, max_workspace_mb=256):
+        """Which past steps, and which features, make the encoder assign a vehicle its intent: the derivative of the latent
+        ``latent_trace`` returns with respect to the RAW history, by BPTT through the encoder chain (csrc/enc_saliency.hip).
+        history [E, T, nA, N, d] as for ``latent_trace`` (numpy in -> numpy out, device tensor in -> device tensors out).
+          windows  None = the last window J - 1 (J = T - 1 - L), an int, or a sorted sequence of distinct ints in [0, J); W = their number
+          lags     K, the number of earlier windows that are unrolled; None = max(windows), i.e. everything.  For target window j the
+                   windows j - Kj .. j, Kj = min(K, j), are differentiated and he / latent of window j - Kj - 1 are held constant (both
+                   are zero when Kj = j: the result is then the exact total derivative).  R = K + L steps are reported.
+          target   the cotangent v of y = <v, lat_j>: "argmax" = one-hot of the chain's own argmax_z lat_j (lowest index on ties; returned
+                   as target_index), an int z = that component everywhere, or a float tensor [E, W, nA, N, Z] -- e.g. the ``beh`` columns
+                   of ``DcntrlMAC.saliency(..., want=("input_grad",))``'s actor_input_grad, which continues the policy's saliency back to
+                   the history
+          want     any of "step", "grad", "act"
+        With G[r, c] = d y / d x_{j-r, c}, returns a dict of
+          step_l1, step_gxi [E, W, nA, N, R]   sum_c |G[r, c]|  and  sum_c G[r, c] x_{j-r, c}                       ("step")
+          feature_l1        [E, W, nA, N, d]   sum_r |G[r, c]|                                                     ("step")
+          grad              [E, W, nA, N, R, d]                                                                    ("grad")
+          active            [E, W, nA, N, K+1, L] int64: bit m = unit m of the encoder's input Linear is past its ReLU at recomputed
+                            window j - k, position t; 0 where that window does not exist                           ("act")
+          latent            [E, W, nA, N, Z]   lat_j of the target windows
+          step_valid        [W, R] bool        entries that exist: j - r >= 0 and r <= Kj + L - 1; G is exactly 0 elsewhere
+          target_index      [E, W, nA, N] int64 (target="argmax")
+          carry_l2          [E, W, nA, N]      || d y / d he_{j-Kj-1} ||_2, what still flows into the state beyond the truncation (0 where Kj = j)
+          lag_l1            [nA, R] float64    the mean of step_l1[..., r] over the (env, window, vehicle) entries that are valid and, with
+                            ``presence_col`` not None, have x_j[presence_col] != 0; 0 where nothing counts -- "how far back does the intent look"
+        Envs (and, where one env does not fit, windows) are processed in chunks so that the kernel's scratch stays under
+        ``max_workspace_mb``; chunked and unchunked calls give the same bits.  Deterministic; draws from no generator; no parameter,
+        gradient, optimiser or carried state is touched; a data-parallel ``dp`` attachment is not consulted."""
+        self.join_decoder()
+        as_np = isinstance(history, np.ndarray)
+        if not as_np and not torch.is_tensor(history):
+            raise ValueError("latent_saliency: history must be a numpy array or a tensor [E, T, nA, N, d]")
+        if history.ndim != 5:
+            raise ValueError(f"latent_saliency: history must be [E, T, nA, N, d], got {tuple(history.shape)}")
+        E, T, nA, N, d = (int(s) for s in history.shape)
+        Lw, Z, dev = self.max_history_len, self.latent_dim, self.device
+        J = T - 1 - Lw
+        if nA != self.n_agents or d != self.args.obs_shape_single or E < 1 or N < 1:
+            raise ValueError(f"latent_saliency: history {tuple(history.shape)} does not fit n_agents={self.n_agents}, d={self.args.obs_shape_single}")
+        if J < 1:
+            raise ValueError(f"latent_saliency: T={T} leaves no window (J = T - 1 - L = {J})")
+        if Lw > ops.L.ENC_SAL_MAX_L:
+            raise NotImplementedError(f"latent_saliency: max_history_len={Lw} > {ops.L.ENC_SAL_MAX_L} is not supported by iplan_enc_saliency")
+
+        def as_int(v, what):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"latent_saliency: {what} must be an int, got {v!r}")
+            return int(v)
+        if windows is None:
+            win = [J - 1]
+        elif isinstance(windows, (int, np.integer)) and not isinstance(windows, (bool, np.bool_)):
+            win = [int(windows)]
+        else:
+            try:
+                win = [as_int(j, "a window") for j in list(windows)]
+            except TypeError:
+                raise ValueError(f"latent_saliency: windows must be None, an int or a sequence of ints, got {windows!r}") from None
+        if not win or any(j < 0 or j >= J for j in win) or any(b <= a for a, b in zip(win, win[1:])):
+            raise ValueError(f"latent_saliency: windows must be sorted, distinct and inside [0, J={J}), got {win}")
+        W = len(win)
+        K = max(win) if lags is None else as_int(lags, "lags")
+        if K < 0:
+            raise ValueError(f"latent_saliency: lags={K} is negative")
+        R = K + Lw
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if any(k not in ("step", "grad", "act") for k in want):
+            raise ValueError(f"latent_saliency: want={want} -- known: 'step', 'grad', 'act'")
+        if presence_col is not None and not 0 <= as_int(presence_col, "presence_col") < d:
+            raise ValueError(f"latent_saliency: presence_col={presence_col} outside [0, d={d})")
+        seed_index, seed_full = -1, None
+        if isinstance(target, str):
+            if target != "argmax":
+                raise ValueError(f"latent_saliency: target={target!r} -- 'argmax', an int or a tensor [E, W, nA, N, Z]")
+        elif isinstance(target, (int, np.integer)) and not isinstance(target, (bool, np.bool_)):
+            seed_index = int(target)
+            if not 0 <= seed_index < Z:
+                raise ValueError(f"latent_saliency: target={seed_index} outside [0, Z={Z})")
+        elif isinstance(target, np.ndarray) or torch.is_tensor(target):
+            if tuple(target.shape) != (E, W, nA, N, Z) or not (torch.as_tensor(target).dtype.is_floating_point):
+                raise ValueError(f"latent_saliency: a target tensor must be float [E, W, nA, N, Z] = {(E, W, nA, N, Z)}, got {tuple(target.shape)}")
+            seed_full = _as_dev(target, dev)
+        else:
+            raise ValueError(f"latent_saliency: target={target!r} -- 'argmax', an int or a tensor [E, W, nA, N, Z]")
+        if not (isinstance(max_workspace_mb, (int, float)) and max_workspace_mb > 0):
+            raise ValueError(f"latent_saliency: max_workspace_mb={max_workspace_mb!r} must be positive")
+
+        h = _as_dev(history, dev)
+        hist = h.permute(2, 0, 1, 3, 4)                                            # [nA, E, T, N, d] view
+        if hist.stride(4) != 1 or hist.stride(3) != d:
+            hist = hist.contiguous()
+        names = ["step_l1", "carry_l2", "latent"]
+        names += ["step_gxi", "feature_l1"] if "step" in want else []
+        names += ["grad"] if "grad" in want else []
+        names += ["active"] if "act" in want else []
+        names += ["target_index"] if seed_full is None and seed_index < 0 else []
+        tail = dict(grad=(R, d), step_l1=(R,), step_gxi=(R,), feature_l1=(d,), carry_l2=(), latent=(Z,), target_index=(), active=(K + 1, Lw))
+        # chunks: envs first; where ONE env with all windows does not fit, groups of windows as well.  Counted against the limit: the
+        # kernel's scratch (he_j of windows 0 .. max(windows), one index per slot) and the chunk's own output buffers.
+        limit = int(max_workspace_mb * 2 ** 20) // 4
+        out_w = nA * N * sum(int(np.prod(tail[k])) for k in names)                  # output floats per env and window
+        he_env = ops.enc_saliency_scratch_floats(nA, N, win[-1:]) - nA * N           # scratch floats per env that all windows share
+        per_env = he_env + W * (nA * N + out_w)
+        if per_env <= limit:
+            Ec, groups = min(E, limit // per_env), [(0, W)]
+        else:
+            Ec, g = 1, (limit - he_env) // (nA * N + out_w)
+            if g < 1:
+                raise ValueError(f"latent_saliency: max_workspace_mb={max_workspace_mb} is too small for one env and one window "
+                                 f"({4 * (he_env + nA * N + out_w)} bytes)")
+            groups = [(w, min(W, w + g)) for w in range(0, W, g)]
+        full = {k: torch.empty((nA, E, N, W) + tail[k], dtype=torch.int32 if k in ("target_index", "active") else torch.float32, device=dev)
+                for k in names}
+        for e0 in range(0, E, Ec):
+            e1 = min(E, e0 + Ec)
+            for w0, w1 in groups:
+                seed = None
+                if seed_full is not None:
+                    seed = seed_full[e0:e1, w0:w1].permute(2, 0, 3, 1, 4).reshape(nA, (e1 - e0) * N, w1 - w0, Z).contiguous()
+                out = ops.enc_saliency(self.enc_arena, hist[:, e0:e1], win[w0:w1], K, Lw, Z, self.soft_update_coef, seed=seed,
+                                       seed_index=seed_index, want=names)
+                for k in names:
+                    full[k][:, e0:e1, :, w0:w1] = out[k].reshape((nA, e1 - e0, N, w1 - w0) + tail[k])
+        jw = torch.tensor(win, device=dev)
+        r = torch.arange(R, device=dev)
+        Kj = torch.clamp(jw, max=K)
+        step_valid = (r[None, :] <= jw[:, None]) & (r[None, :] <= (Kj + Lw - 1)[:, None])         # [W, R]
+        counted = step_valid[None, None, None].expand(nA, E, N, W, R)
+        if presence_col is not None:
+            counted = counted & (hist[..., presence_col].index_select(2, jw).permute(0, 1, 3, 2) != 0)[..., None]
+        cnt = counted.sum(dim=(1, 2, 3)).double()                                                 # [nA, R]
+        num = (full["step_l1"].double() * counted).sum(dim=(1, 2, 3))
+        lag_l1 = torch.where(cnt > 0, num / cnt.clamp(min=1.0), torch.zeros_like(num))
+        res = {k: full[k].permute(*((1, 3, 0, 2) + tuple(range(4, full[k].dim())))) for k in names}
+        if "step" not in want:
+            del res["step_l1"]
+        if "active" in res:
+            res["active"] = res["active"].to(torch.int64) & 0xFFFFFFFF
+        if "target_index" in res:
+            res["target_index"] = res["target_index"].to(torch.int64)
+        res["step_valid"], res["lag_l1"] = step_valid, lag_l1
+        if not as_np:
+            return res
+        # numpy callers: ONE read-back (every piece is exactly representable in float64)
+        keys = list(res)
+        host = torch.cat([res[k].reshape(-1).double() for k in keys]).cpu().numpy()
+        out_np, at = {}, 0
+        for k in keys:
+            n = res[k].numel()
+            piece = host[at:at + n].reshape(tuple(res[k].shape))
+            at += n
+            out_np[k] = piece.astype({torch.float32: np.float32, torch.int64: np.int64, torch.bool: np.bool_}.get(res[k].dtype, np.float64))
+        return out_np
+
     # ---------------------------------------------------------------------------- checkpoints
     def save_models(self, path):
         self.join_decoder()

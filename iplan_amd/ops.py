@@ -1568,6 +1568,67 @@ def beh_eval(enc_arena, dec_arena, hist, mask, L_win, Z, coef, thres, want_laten
     return out
 
 
+def enc_saliency_scratch_floats(n_nets, rows, windows):
+    """floats of caller scratch ``iplan_enc_saliency`` needs: he_j of windows 0 .. max(windows) and one index per slot; independent of K"""
+    return n_nets * rows * ((max(windows) + 1) * 32 + len(windows))
+
+
+ENC_SAL_OUTPUTS = ("grad", "step_l1", "step_gxi", "feature_l1", "carry_l2", "latent", "target_index", "active")
+
+
+def enc_saliency(enc_arena, hist, windows, K, L_win, Z, coef, seed=None, seed_index=-1, want=("grad",), out=None, lib=None):
+    """d <v, lat_j> / d x_{j-r}: BPTT through the behaviour encoder's chain back to the raw history (csrc/enc_saliency.hip), for all
+    nets, every (env, entity) chain and every target window j in ``windows`` (sorted, distinct ints in [0, J), J = T - 1 - L_win).
+    hist [n_nets, E, T, N, d] (first three dims may be strided); ``K`` earlier windows are unrolled, R = K + L_win; the cotangent v is
+    ``seed`` [n_nets, E*N, nW, Z] or, with ``seed=None``, the one-hot of ``seed_index`` (-1: the chain's own argmax of lat_j).
+    ``want``: names out of ENC_SAL_OUTPUTS.  Returns a dict with grad [n_nets, E*N, nW, R, d], step_l1 / step_gxi [n_nets, E*N, nW, R],
+    feature_l1 [n_nets, E*N, nW, d], carry_l2 [n_nets, E*N, nW], latent [n_nets, E*N, nW, Z], target_index int32 [n_nets, E*N, nW],
+    active int32 [n_nets, E*N, nW, K+1, L_win] (a 32-bit mask), None for what was not asked for.  ``out``: optional dict of
+    destination tensors of exactly those shapes (contiguous) for some of the wanted names."""
+    lib = _lib(lib)
+    n_nets, E, T, N, d = hist.shape
+    assert hist.dtype == torch.float32 and hist.stride(4) == 1 and hist.stride(3) == d
+    assert all(k in ENC_SAL_OUTPUTS for k in want), want
+    dev = hist.device
+    windows = [int(j) for j in windows]
+    nW, rows, R = len(windows), E * N, K + L_win
+    a = L.EncSaliencyArgs()
+    a.n_nets, a.E, a.N, a.T, a.L, a.d, a.Z, a.K, a.nW = n_nets, E, N, T, L_win, d, Z, K, nW
+    a.hist, a.h_s_net, a.h_s_e, a.h_s_t = hist.data_ptr(), hist.stride(0), hist.stride(1), hist.stride(2)
+    # the kernel reads steps 0 .. max(windows) of every (net, env): they must lie inside the history's storage
+    if nW and 0 <= max(windows) < T and min(hist.stride(0), hist.stride(1), hist.stride(2)) >= 0:
+        _inside(hist, (n_nets - 1) * hist.stride(0) + (E - 1) * hist.stride(1) + max(windows) * hist.stride(2) + N * d, "enc_saliency: hist")
+    w_host = (C.c_int32 * max(nW, 1))(*windows)
+    w_dev = torch.tensor(windows, dtype=torch.int32, device=dev) if nW else None
+    a.windows, a.windows_host = L.ptr(w_dev), C.cast(w_host, C.c_void_p)
+    if seed is not None:
+        assert seed.dtype == torch.float32 and seed.device == dev and seed.is_contiguous() and seed.shape == (n_nets, rows, nW, Z), seed.shape
+        a.seed = seed.data_ptr()
+    a.seed_index, a.coef = int(seed_index), coef
+    a.enc_params, a.enc_s_net = enc_arena.data.data_ptr(), enc_arena.net_stride
+    for i, k in enumerate(L.ENC_PARAM_ORDER):
+        a.enc_off[i] = enc_arena.off(k)
+    floats = enc_saliency_scratch_floats(n_nets, rows, windows) if nW and 0 <= max(windows) < T else 0
+    scratch = torch.empty(max(floats, 4), dtype=torch.float32, device=dev)      # (an inspection call: not kept between calls)
+    a.scratch, a.scratch_floats = scratch.data_ptr(), floats
+    shapes = dict(grad=(R, d), step_l1=(R,), step_gxi=(R,), feature_l1=(d,), carry_l2=(), latent=(Z,), target_index=(), active=(K + 1, L_win))
+    res = {k: None for k in ENC_SAL_OUTPUTS}
+    for k in want:
+        shape = (n_nets, rows, nW) + shapes[k]
+        dt = torch.float32 if k not in ("target_index", "active") else torch.int32
+        if out is not None and k in out:
+            t = out[k]
+            assert t.shape == shape and t.dtype == dt and t.is_contiguous() and t.device == dev, (k, t.shape, shape)
+        else:
+            t = torch.empty(shape, dtype=dt, device=dev)
+        res[k] = t
+        setattr(a, k, t.data_ptr())
+    _launch("enc_saliency_kernel", lambda: lib.call("iplan_enc_saliency", a, L.current_stream(dev)))
+    res["_args"] = a
+    res["_keep"] = (hist, w_host, w_dev, seed, scratch)
+    return res
+
+
 def beh_backward(enc_arena, dec_arena, fwd, accumulate=False, penalty=0.0, E_norm=0, defer_dec_wgrad=False, lib=None):
     """BPTT of beh_forward's behaviour loss: fills both gradient arenas (``accumulate=True``: adds to them -- launches on
     disjoint env chunks of one batch, normalised by a shared ``win_norm``).
