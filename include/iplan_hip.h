@@ -1252,6 +1252,45 @@ typedef struct {
 } IplanObsHistArgs;
 int iplan_obs_history_step(const IplanObsHistArgs* args, iplan_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Attention saliency: the input backward of GAT_Net.forward with the egos kept apart (csrc/gat_saliency.hip).  For every scene
+ * (net, b) and every ego i:  y_i = <v_i, latent_i>,  latent = GAT([src0 || src1], h_prev) as the training-form forward launch
+ * described by `fwd` computed it (its `saved` record filled; h_prev is held constant), and
+ *   G[i, j, c] = d y_i / d obs[j, c]     for every entity j of the scene, the ego included, and every column c < d0 + d1.
+ * v: rows of A floats, (net, b, i) at v + net*v_s_net + b*v_s_b + i*A.
+ * gate_through: 1 = the exact derivative, through the gumbel gate and the bidirectional pair GRU (1/tau included); 0 = the gate is
+ * held constant: only the soft attention, the values and the output cell are differentiated, saved.gru and scratch are not read.
+ * Outputs, each optional (NULL = not wanted; at least one is), scene (net, b) at base + net*s_net + b*s_b, contiguous inside:
+ *   grad        [N, N, d0 + d1]   G, indexed [ego i, entity j, column]
+ *   pair_gl1    [N, N, n_src]     sum_c |G[i, j, c]| over the columns of source 0 (src0) / 1 (src1); n_src = 2 if d1 > 0 else 1
+ *   pair_gxi    [N, N, n_src]     sum_c G[i, j, c] obs[j, c]                           (both share pair_s_net / pair_s_b)
+ *   input_grad  [N, d0 + d1]      sum_i G[i, j, :]: a running fp32 sum over the egos in ascending order, one rounded add each
+ *   hidden_grad [N, A]            d y_i / d h_prev_i
+ * scratch (gate_through == 1): at least n_nets * B * 2 * N * N * 3H floats, 16-byte aligned.
+ * One workgroup per scene, no atomics, no sums across scenes: a scene's bits depend on its own operands only -- not on the other
+ * scenes of the launch, its position among them, or on which outputs were asked for.  An ego with v_i == 0 gets exact zeros.
+ * 2 <= N <= IPLAN_MAX_ENTITIES, d0 >= 1, d1 >= 0.  Parameters, the record and the inputs are only read.
+ */
+typedef struct {
+    IplanGatFwdArgs fwd;
+    const float* v;
+    int64_t v_s_net, v_s_b;
+    int32_t gate_through;
+    float* scratch;
+    int64_t scratch_floats;
+    float* grad;
+    int64_t grad_s_net, grad_s_b;
+    float* pair_gl1;
+    float* pair_gxi;
+    int64_t pair_s_net, pair_s_b;
+    float* input_grad;
+    int64_t ig_s_net, ig_s_b;
+    float* hidden_grad;
+    int64_t hg_s_net, hg_s_b;
+} IplanGatSaliencyArgs;
+
+int iplan_gat_saliency(const IplanGatSaliencyArgs* args, iplan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

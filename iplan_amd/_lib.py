@@ -53,7 +53,8 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_pdec_fwd", "iplan_pdec_bwd", "iplan_beh_fwd", "iplan_beh_bwd", "iplan_mlp3_fwd", "iplan_mlp3_bwd", "iplan_seq2seq_fwd", "iplan_ac_pack_fc1",
                 "iplan_ac_xhat_pack", "iplan_ac_fc1_split_fwd", "iplan_ac_bwd_fc1_split",
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
-                "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency"]
+                "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
+                "iplan_gat_saliency"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -443,6 +444,20 @@ class GatTraceArgs(C.Structure):
     ]
 
 
+GAT_MAX_ENTITIES = 64    # IPLAN_MAX_ENTITIES
+
+
+class GatSaliencyArgs(C.Structure):
+    _fields_ = [
+        ("fwd", GatFwdArgs), ("v", fp), ("v_s_net", i64), ("v_s_b", i64), ("gate_through", i32),
+        ("scratch", fp), ("scratch_floats", i64),
+        ("grad", fp), ("grad_s_net", i64), ("grad_s_b", i64),
+        ("pair_gl1", fp), ("pair_gxi", fp), ("pair_s_net", i64), ("pair_s_b", i64),
+        ("input_grad", fp), ("ig_s_net", i64), ("ig_s_b", i64),
+        ("hidden_grad", fp), ("hg_s_net", i64), ("hg_s_b", i64),
+    ]
+
+
 AC_TRACE_GI = 3 * AC_HIDDEN      # IPLAN_AC_TRACE_GI
 
 
@@ -519,4 +534,4 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanObsHistArgs": ObsHistArgs, "IplanPredictArgs": PredictArgs, "IplanBehEvalArgs": BehEvalArgs,
                   "IplanGatTraceArgs": GatTraceArgs, "IplanAcTraceArgs": AcTraceArgs, "IplanPpoEvalArgs": PpoEvalArgs,
                   "IplanAcSaliencyArgs": AcSaliencyArgs, "IplanAcSaliencyLagArgs": AcSaliencyLagArgs,
-                  "IplanEncSaliencyArgs": EncSaliencyArgs}
+                  "IplanEncSaliencyArgs": EncSaliencyArgs, "IplanGatSaliencyArgs": GatSaliencyArgs}

@@ -259,9 +259,9 @@ class DcntrlMAC:
         Device tensors in -> device tensors out, numpy in -> numpy out.  Draws from no generator; parameters, gradient entries,
         optimiser state, ``hidden_states`` and the batch are not touched; the packed fc1 operands are brought up to date exactly as
         ``policy_trace`` does it (the values any later launch would pack), the kernel only reads them.  Not covered: layer_N /
-        recurrent_N other than 1, saliency through the GAT back to the raw history (the behaviour-encoder half is
-        ``Behavior_policy.latent_saliency``: hand it the ``beh`` columns of ``actor_input_grad`` as ``target``; the GAT half is still
-        open); through time: ``saliency_trace``."""
+        recurrent_N other than 1.  Back to the raw history: hand the ``beh`` columns of ``actor_input_grad`` to
+        ``Behavior_policy.latent_saliency`` and the ``att`` columns to ``Prediction_policy.attention_saliency`` as ``target``;
+        through time: ``saliency_trace``."""
         a = self.args
         if a.layer_N != 1 or a.recurrent_N != 1:
             raise NotImplementedError("saliency covers layer_N = recurrent_N = 1 only")
@@ -366,9 +366,9 @@ class DcntrlMAC:
           actor_act1, actor_act2, critic_act1, critic_act2 [E, S, nA, M]  with "act" in ``want`` (tests)
           actor_carry, critic_carry [E, S, K+1, nA, M]  with "carry" in ``want``: d y_s / d h_{s-k-1} itself
         Device tensors in -> device tensors out, numpy in -> numpy out.  Draws from no generator; parameters, gradient entries,
-        optimiser state, ``hidden_states`` and the batch are not touched.  Not covered: layer_N / recurrent_N other than 1, saliency
-        through the GAT back to the raw history (the behaviour-encoder half is ``Behavior_policy.latent_saliency``; the GAT half is
-        still open)."""
+        optimiser state, ``hidden_states`` and the batch are not touched.  Not covered: layer_N / recurrent_N other than 1.  Back to
+        the raw history: ``Behavior_policy.latent_saliency`` (the ``beh`` columns) and ``Prediction_policy.attention_saliency`` (the
+        ``att`` columns)."""
         a = self.args
         if a.layer_N != 1 or a.recurrent_N != 1:
             raise NotImplementedError("saliency_trace covers layer_N = recurrent_N = 1 only")

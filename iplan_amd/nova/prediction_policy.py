@@ -314,6 +314,135 @@ class Prediction_policy:
             return r
         return finish if defer else finish()
 
+    # ---------------------------------------------------------------------------- attention saliency
+    def attention_saliency(self, history, behavior_latent=None, hidden=None, target="self", noise=None, deterministic=True,
+                           gate="through", tau=None, want=("pair",), max_workspace_mb=256):
+        """How much do the inputs of entity j move the attention latent of ego i?  For every row (env, step, agent) of ``history``
+        [E,S,nA,N,d] (with ``behavior_latent`` [E,S,nA,N,Z]; needed with ``GAT_use_behavior``, ignored without) and every ego i:
+            y_i = <v_i, latent_i>,  latent = GAT([history || behavior_latent], hidden),  G[i, j, c] = d y_i / d obs[j, c]
+        for every entity j, the ego included, and every column c of [hist || beh].  ``hidden`` [E,S,nA,N,A] is the state each row
+        starts from (None: zeros; for a recorded batch ``attention_latent[:, :-1]`` with ``attention_trace``'s alignment); it is
+        held constant, so the rows are independent and nothing is differentiated through time.
+        ``target``: "self" -> v_i = latent_i (the gradient of 1/2 |latent_i|^2); an int -> the one-hot of that unit; a tensor
+        [E,S,nA,N,A] -> used as given (e.g. the ``att`` columns of ``DcntrlMAC.saliency``'s ``actor_input_grad``).
+        ``deterministic=True`` uses no gumbel noise and draws nothing (the gate is sigmoid((l1 - l0) / tau)); otherwise ``noise``
+        [nA,E,S,N,N-1,2] is used, or drawn from torch's generator.  ``gate``: "through" = the exact derivative, 1/tau included;
+        "held" = the gate is a constant (only the soft attention, the values and the output cell are differentiated).  ``tau``:
+        None = the policy's own 0.01.
+        Returns a dict; the pair tensors are indexed [ego i, entity j], n_src = 2 with ``GAT_use_behavior`` else 1:
+          ``pair_gl1``, ``pair_gxi`` [E,S,nA,N,N,n_src]  sum_c |G[i,j,c]| and sum_c G[i,j,c] obs[j,c] per source ("pair" in ``want``)
+          ``grad`` [E,S,nA,N,N,d+Z]                      all of G ("grad" in ``want``)
+          ``input_grad`` [E,S,nA,N,d+Z]                  sum_i G[i,j,:] -- continues the policy's saliency to the GAT's inputs
+          ``hidden_grad`` [E,S,nA,N,A]                   d y_i / d hidden_i
+          ``latent``, ``target_vector`` [E,S,nA,N,A]     the forward result (the rollout's bits) and the v used
+          ``active_h``, ``active_v`` [E,S,nA,N,32] bool  the ReLU branches of ``encoding`` and ``v`` the backward used
+        The rows go through the training-form GAT forward and ``iplan_gat_saliency`` in chunks whose record and scratch stay
+        under ``max_workspace_mb`` (the pair-GRU record alone is 3.5 MB per scene at 55 entities); a row's bits do not depend
+        on the chunking.  numpy in -> numpy out, device tensors in -> device tensors out.  Parameters, gradients, optimiser
+        state and (with ``deterministic=True``) torch's generator are not touched."""
+        as_np = isinstance(history, np.ndarray)
+        dev = self.device
+        hist = _as_dev(history, dev)
+        if hist.dim() != 5:
+            raise ValueError(f"attention_saliency: history must be [E,S,nA,N,d], got {tuple(hist.shape)}")
+        E, S, nA, N, d = hist.shape
+        A = self.args.attention_dim
+        if nA != self.n_agents or d != self.obs_shape or not 2 <= N <= ops.L.GAT_MAX_ENTITIES:
+            raise ValueError(f"attention_saliency: history {tuple(hist.shape)} does not fit n_agents={self.n_agents}, obs width {self.obs_shape}, "
+                             f"2 <= N <= {ops.L.GAT_MAX_ENTITIES}")
+        if gate not in ("through", "held"):
+            raise ValueError(f"attention_saliency: gate={gate!r} is neither 'through' nor 'held'")
+        want = tuple(want)
+        if any(k not in ("pair", "grad") for k in want):
+            raise ValueError(f"attention_saliency: want={want} -- known: 'pair', 'grad'")
+        if deterministic and noise is not None:
+            raise ValueError("attention_saliency: noise was given together with deterministic=True")
+        tau = 0.01 if tau is None else float(tau)
+        if not tau > 0:
+            raise ValueError(f"attention_saliency: tau={tau} must be positive")
+        B = E * S
+        Z = 0
+        lat = None
+        if self.args.GAT_use_behavior:
+            if behavior_latent is None:
+                raise ValueError("attention_saliency: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
+            lat = _as_dev(behavior_latent, dev)
+            Z = self.args.latent_dim
+            if lat.shape != (E, S, nA, N, Z):
+                raise ValueError(f"attention_saliency: behavior_latent {tuple(lat.shape)} != {(E, S, nA, N, Z)}")
+            lat = lat.permute(2, 0, 1, 3, 4).reshape(nA, B, N, Z).contiguous()
+        D = d + Z
+        n_src = 2 if Z else 1
+        src0 = hist.permute(2, 0, 1, 3, 4).reshape(nA, B, N, d).contiguous()          # rows (agent, env * S + step): data movement only
+        if hidden is None:
+            hid = torch.zeros(nA, B, N, A, dtype=torch.float32, device=dev)
+        else:
+            hid = _as_dev(hidden, dev)
+            if hid.shape != (E, S, nA, N, A):
+                raise ValueError(f"attention_saliency: hidden {tuple(hid.shape)} != {(E, S, nA, N, A)}")
+            hid = hid.permute(2, 0, 1, 3, 4).reshape(nA, B, N, A).contiguous()
+        if noise is not None:
+            noise = _as_dev(noise, dev)
+            if noise.shape != (nA, E, S, N, N - 1, 2):
+                raise ValueError(f"attention_saliency: noise {tuple(noise.shape)} != {(nA, E, S, N, N - 1, 2)}")
+            noise = noise.reshape(nA, B, N, N - 1, 2)
+        vt = None
+        if isinstance(target, str):
+            if target != "self":
+                raise ValueError(f"attention_saliency: target={target!r} -- 'self', a unit index or a tensor [E,S,nA,N,A]")
+        elif isinstance(target, (int, np.integer)) and not isinstance(target, bool):
+            if not 0 <= int(target) < A:
+                raise ValueError(f"attention_saliency: target unit {target} outside [0, {A})")
+            vt = torch.zeros(nA, B, N, A, dtype=torch.float32, device=dev)
+            vt[..., int(target)] = 1.0
+        elif isinstance(target, (np.ndarray, torch.Tensor)):
+            vt = _as_dev(target, dev)
+            if vt.shape != (E, S, nA, N, A):
+                raise ValueError(f"attention_saliency: target {tuple(vt.shape)} != {(E, S, nA, N, A)}")
+            vt = vt.permute(2, 0, 1, 3, 4).reshape(nA, B, N, A).contiguous()
+        else:
+            raise ValueError(f"attention_saliency: target={target!r} -- 'self', a unit index or a tensor [E,S,nA,N,A]")
+        through = gate == "through"
+        # bytes of record, scratch and noise one row (all agents) holds while its chunk is in flight
+        per_row = 4 * nA * (2 * ((N + 15) // 16) * (N - 1) * 2048 + N * (8 * A + 2 * (N - 1)) + 2 * N * (N - 1)
+                            + (ops.gat_saliency_scratch_floats(1, 1, N) if through else 0))
+        chunk = int(max_workspace_mb * (1 << 20)) // per_row
+        if chunk < 1:
+            raise ValueError(f"attention_saliency: max_workspace_mb={max_workspace_mb} is too small for one row ({per_row / (1 << 20):.1f} MB)")
+        f32 = dict(dtype=torch.float32, device=dev)
+        res = {"input_grad": torch.empty(nA, B, N, D, **f32), "hidden_grad": torch.empty(nA, B, N, A, **f32),
+               "latent": torch.empty(nA, B, N, A, **f32)}
+        if "pair" in want:
+            res["pair_gl1"] = torch.empty(nA, B, N, N, n_src, **f32)
+            res["pair_gxi"] = torch.empty(nA, B, N, N, n_src, **f32)
+        if "grad" in want:
+            res["grad"] = torch.empty(nA, B, N, N, D, **f32)
+        res["target_vector"] = vt if vt is not None else res["latent"]
+        act_h = torch.empty(nA, B, N, A, dtype=torch.bool, device=dev)
+        act_v = torch.empty(nA, B, N, A, dtype=torch.bool, device=dev)
+        outs = tuple(k for k in ops.GAT_SALIENCY_OUTPUTS if k in res)
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            if deterministic:
+                nz = torch.zeros(nA, b1 - b0, N, N - 1, 2, **f32)                  # l + 0 is exact: the gate of no noise
+            elif noise is not None:
+                nz = noise[:, b0:b1].contiguous()
+            else:
+                nz = gumbel_noise((nA, b1 - b0, N, N - 1, 2), dev)
+            s0, s1, h0 = src0[:, b0:b1], None if lat is None else lat[:, b0:b1], hid[:, b0:b1]
+            # the rollout's bits of the latent: the inference form of the forward (attention_map's launch)
+            ops.gat_trace(self.gat_arena, s0.unsqueeze(2), None if s1 is None else s1.unsqueeze(2), h0, None if deterministic else nz.unsqueeze(2),
+                          tau=tau, want=("latent",), out={"latent": res["latent"][:, b0:b1].unsqueeze(2)})
+            # the record the backward reads: the training form of the same forward
+            _, saved = ops.gat_forward(self.gat_arena, s0, s1, h0, nz, tau=tau, save=True)
+            ops.gat_saliency(self.gat_arena, saved, res["target_vector"][:, b0:b1], gate_through=through, want=outs,
+                             out={k: res[k][:, b0:b1] for k in outs})
+            act_h[:, b0:b1] = saved["h_enc"].view(nA, b1 - b0, N, A) > 0
+            act_v[:, b0:b1] = saved["qkv"].view(nA, b1 - b0, N, 3 * A)[..., 2 * A:] > 0
+        res["active_h"], res["active_v"] = act_h, act_v
+        res = {k: v.unflatten(1, (E, S)).permute(1, 2, 0, *range(3, v.dim() + 1)) for k, v in res.items()}
+        return {k: v.cpu().numpy() for k, v in res.items()} if as_np else res
+
     # ---------------------------------------------------------------------------- learning
     def _sample(self, n_thread, avail_len):
         """The host-side random draws of one agent in the reference's order: the (episode, t) sample of

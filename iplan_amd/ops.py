@@ -207,6 +207,77 @@ def gat_trace_args(arena, src0, src1=None, hidden0=None, noise=None, tau=0.01, w
     return a, res
 
 
+GAT_SALIENCY_OUTPUTS = ("grad", "pair_gl1", "pair_gxi", "input_grad", "hidden_grad")
+
+
+def gat_saliency_scratch_floats(n_nets, B, N):
+    """floats of scratch an exact-gate ``gat_saliency`` launch needs: [dr dz dn_i] of every pair step of both directions + their sums"""
+    return n_nets * B * 2 * N * N * 3 * 32
+
+
+def gat_saliency(arena, saved, v, gate_through=True, want=("input_grad",), out=None, scratch=None, lib=None):
+    """The input backward of a ``gat_forward(..., save=True)`` launch with the egos kept apart (iplan_gat_saliency): for every
+    scene and ego i, G[i, j, :] = d <v_i, latent_i> / d [src0 || src1][j].  ``saved``: what that forward returned; v [n_nets,B,N,A]
+    (first two dims strided).  ``gate_through=False`` holds the gumbel gate constant (the pair-GRU record is not read).  ``want``:
+    which of grad [n_nets,B,N,N,D], pair_gl1 / pair_gxi [n_nets,B,N,N,n_src], input_grad [n_nets,B,N,D], hidden_grad [n_nets,B,N,A]
+    to produce; ``out``: optional dict of destination views for some of them (first two dims strided, inside their storage);
+    ``scratch``: optional float32 buffer of at least ``gat_saliency_scratch_floats`` floats.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res, keep = gat_saliency_args(arena, saved, v, gate_through, want, out, scratch)
+    _launch("gat_saliency_kernel", lambda: lib.call("iplan_gat_saliency", a, L.current_stream(v.device)))
+    res["_keep"] = keep
+    return res
+
+
+def gat_saliency_args(arena, saved, v, gate_through=True, want=("input_grad",), out=None, scratch=None):
+    """The descriptor of a ``gat_saliency`` launch, its output tensors and what must stay alive until the launch has been queued,
+    checked but not launched: (IplanGatSaliencyArgs, dict, list)."""
+    fa = saved["_args"]
+    n_nets, B, N, d0, d1 = fa.n_nets, fa.B, fa.N, fa.d0, fa.d1
+    A, D, n_src = 32, d0 + d1, 2 if d1 > 0 else 1
+    dev = v.device
+    want = tuple(want)
+    assert want and all(k in GAT_SALIENCY_OUTPUTS for k in want), want
+    assert fa.params == arena.data.data_ptr(), "saved belongs to another arena"
+    a = L.GatSaliencyArgs()
+    a.fwd = fa
+    assert v.shape == (n_nets, B, N, A) and v.dtype == torch.float32, (v.shape, v.dtype)
+    a.v = v.data_ptr()
+    a.v_s_net, a.v_s_b, _ = _nbs_strides(v.unsqueeze(2), N * A, "v")
+    a.gate_through = 1 if gate_through else 0
+    keep = [saved, v]
+    if gate_through:
+        need = gat_saliency_scratch_floats(n_nets, B, N)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.float32, device=dev)
+        assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= need and scratch.device == dev, (scratch.numel(), need)
+        a.scratch, a.scratch_floats = scratch.data_ptr(), scratch.numel()
+        keep.append(scratch)
+    res = {}
+    inner = {"grad": (N, N, D), "pair_gl1": (N, N, n_src), "pair_gxi": (N, N, n_src), "input_grad": (N, D), "hidden_grad": (N, A)}
+    pre = {"grad": "grad", "input_grad": "ig", "hidden_grad": "hg"}
+    pair = None
+    for k in want:
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.empty(n_nets, B, *inner[k], dtype=torch.float32, device=dev)
+        assert t.shape == (n_nets, B) + inner[k] and t.device == dev, (k, t.shape)
+        n_in = 1
+        for x in inner[k]:
+            n_in *= x
+        s_net, s_b, _ = _nbs_strides(t.unsqueeze(2), n_in, k)
+        setattr(a, k, t.data_ptr())
+        if k in pre:
+            setattr(a, pre[k] + "_s_net", s_net)
+            setattr(a, pre[k] + "_s_b", s_b)
+        else:
+            assert pair is None or pair == (s_net, s_b), "pair_gl1 and pair_gxi share their strides"
+            pair = (s_net, s_b)
+            a.pair_s_net, a.pair_s_b = s_net, s_b
+        res[k] = t
+    return a, res, keep
+
+
 _FUSED_SYNC = {}
 
 
