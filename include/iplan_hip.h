@@ -1291,6 +1291,55 @@ typedef struct {
 
 int iplan_gat_saliency(const IplanGatSaliencyArgs* args, iplan_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Prediction saliency: the input Jacobian of the chain iplan_predict walks (csrc/pdec_saliency.hip),
+ *   x_0 = start state, h_{-1} = h0;  t < P:  u_t = ReLU(W_lin x_t + b_lin), h_t = GRU32(u_t, h_{t-1}), y_t = W_out tanh(h_t) + b_out, x_{t+1} = y_t
+ * (Prediction_Decoder.forward(last_state, None, hidden) under .eval(): no teacher forcing, no dropout).  Rows, the start state read in
+ * place through offset / ent_stride, h0 and the parameters are iplan_predict's.  A job k < K is the pair jobs[k] = (p, c): horizon step
+ * p in [0, P) and the cotangent v on y_p -- the one-hot of column c in [0, d), or, with c == -1, the row v[net, row, p, :] of the tensor
+ * `v` [n_nets, rows, P, d].  The job list is the same for every row.  For every row and job, by BPTT through steps p .. 0 with the gates
+ * recomputed (nothing is recorded in global memory, whatever P is):
+ *   state_grad  [n_nets, rows, K, d]    d <v, y_p> / d x_0
+ *   latent_grad [n_nets, rows, K, 32]   d <v, y_p> / d h0
+ *   state_l1, state_gxi   [n_nets, rows, K]   sum_c |state_grad[c]|,  sum_c state_grad[c] x_0[c]
+ *   latent_l1, latent_gxi [n_nets, rows, K]   sum_c |latent_grad[c]|, sum_c latent_grad[c] h0[c]
+ *               (one lane per row, c ascending, every product and sum rounded on its own: the plain fp32 loops over the stored gradient)
+ * and, independent of the jobs,
+ *   pred        [n_nets, rows, P, d]    y_t, bit for bit iplan_predict's
+ *   active      [n_nets, rows, P] int32: bit m = unit m of the input Linear has u_t > 0
+ * Each output is optional (NULL = not wanted and not written; at least one is asked for); the per-job ones need K >= 1, jobs (device
+ * memory) and jobs_host (the same values in host memory: argument checks, LDS and grid size).
+ * One wave per (16-row tile, job), one more per tile for pred / active; the weights sit in LDS in both orientations and a wave keeps
+ * the state and input each step enters with in LDS (3 KB per step), which bounds P.  No atomics, no sums across rows: a slot's bits
+ * do not depend on its lane, tile or workgroup, on the other rows, on P, on the other jobs or on which outputs were asked for; two
+ * launches give the same bits; a zero cotangent gives exact zeros; padding lanes of a ragged last tile write nothing; parameters and
+ * inputs are only read.  1 <= d <= 16, hidden == 32, 1 <= P <= IPLAN_PDEC_SAL_MAX_P, n_nets <= IPLAN_MAX_NETS.
+ */
+#define IPLAN_PDEC_SAL_MAX_P 30     /* 160 KB of LDS: 68 KB of weights + one wave's 3 KB per chain step */
+typedef struct {
+    int32_t n_nets, S, N, P, d, K;
+    const float* x0;            /* base of the start states (e.g. the episode buffer's history field)     */
+    const int64_t* offset;      /* [n_nets, S] element offset of (sample, entity 0, feature 0)             */
+    int64_t ent_stride;         /* elements between entities                                               */
+    const float* h0;            /* [n_nets, S*N, 32] GAT output = initial hidden state                     */
+    const float* params;        /* decoder arena, IPLAN_DEC_* offsets                                      */
+    int64_t params_s_net;
+    int64_t off[IPLAN_DEC_NPARAM];
+    const int32_t* jobs;        /* [K, 2] (p, c) in device memory                                          */
+    const int32_t* jobs_host;   /* the same values in host memory                                          */
+    const float* v;             /* [n_nets, S*N, P, d]; needed by jobs with c == -1, NULL otherwise        */
+    float* state_grad;
+    float* latent_grad;
+    float* state_l1;
+    float* state_gxi;
+    float* latent_l1;
+    float* latent_gxi;
+    float* pred;
+    int32_t* active;
+} IplanPdecSaliencyArgs;
+
+int iplan_pdec_saliency(const IplanPdecSaliencyArgs* args, iplan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

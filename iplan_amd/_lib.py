@@ -54,7 +54,7 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_ac_xhat_pack", "iplan_ac_fc1_split_fwd", "iplan_ac_bwd_fc1_split",
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
                 "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
-                "iplan_gat_saliency"]
+                "iplan_gat_saliency", "iplan_pdec_saliency"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -458,6 +458,20 @@ class GatSaliencyArgs(C.Structure):
     ]
 
 
+PDEC_SAL_MAX_P = 30      # IPLAN_PDEC_SAL_MAX_P
+
+
+class PdecSaliencyArgs(C.Structure):
+    _fields_ = [
+        ("n_nets", i32), ("S", i32), ("N", i32), ("P", i32), ("d", i32), ("K", i32),
+        ("x0", fp), ("offset", fp), ("ent_stride", i64), ("h0", fp),
+        ("params", fp), ("params_s_net", i64), ("off", i64 * len(DEC_PARAM_ORDER)),
+        ("jobs", fp), ("jobs_host", fp), ("v", fp),
+        ("state_grad", fp), ("latent_grad", fp), ("state_l1", fp), ("state_gxi", fp), ("latent_l1", fp), ("latent_gxi", fp),
+        ("pred", fp), ("active", fp),
+    ]
+
+
 AC_TRACE_GI = 3 * AC_HIDDEN      # IPLAN_AC_TRACE_GI
 
 
@@ -534,4 +548,5 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanObsHistArgs": ObsHistArgs, "IplanPredictArgs": PredictArgs, "IplanBehEvalArgs": BehEvalArgs,
                   "IplanGatTraceArgs": GatTraceArgs, "IplanAcTraceArgs": AcTraceArgs, "IplanPpoEvalArgs": PpoEvalArgs,
                   "IplanAcSaliencyArgs": AcSaliencyArgs, "IplanAcSaliencyLagArgs": AcSaliencyLagArgs,
-                  "IplanEncSaliencyArgs": EncSaliencyArgs, "IplanGatSaliencyArgs": GatSaliencyArgs}
+                  "IplanEncSaliencyArgs": EncSaliencyArgs, "IplanGatSaliencyArgs": GatSaliencyArgs,
+                  "IplanPdecSaliencyArgs": PdecSaliencyArgs}

@@ -315,6 +315,17 @@ class Prediction_policy:
         return finish if defer else finish()
 
     # ---------------------------------------------------------------------------- attention saliency
+    def _gat_saliency_chunk(self, who, N, through, max_workspace_mb):
+        """rows (one scene per agent each) per chunk of a training-form GAT forward + ``ops.gat_saliency``, such that the record,
+        the scratch and the noise the chunk holds while it is in flight stay under ``max_workspace_mb``"""
+        nA, A = self.n_agents, self.args.attention_dim
+        per_row = 4 * nA * (2 * ((N + 15) // 16) * (N - 1) * 2048 + N * (8 * A + 2 * (N - 1)) + 2 * N * (N - 1)
+                            + (ops.gat_saliency_scratch_floats(1, 1, N) if through else 0))
+        chunk = int(max_workspace_mb * (1 << 20)) // per_row
+        if chunk < 1:
+            raise ValueError(f"{who}: max_workspace_mb={max_workspace_mb} is too small for one row ({per_row / (1 << 20):.1f} MB)")
+        return chunk
+
     def attention_saliency(self, history, behavior_latent=None, hidden=None, target="self", noise=None, deterministic=True,
                            gate="through", tau=None, want=("pair",), max_workspace_mb=256):
         """How much do the inputs of entity j move the attention latent of ego i?  For every row (env, step, agent) of ``history``
@@ -403,12 +414,7 @@ class Prediction_policy:
         else:
             raise ValueError(f"attention_saliency: target={target!r} -- 'self', a unit index or a tensor [E,S,nA,N,A]")
         through = gate == "through"
-        # bytes of record, scratch and noise one row (all agents) holds while its chunk is in flight
-        per_row = 4 * nA * (2 * ((N + 15) // 16) * (N - 1) * 2048 + N * (8 * A + 2 * (N - 1)) + 2 * N * (N - 1)
-                            + (ops.gat_saliency_scratch_floats(1, 1, N) if through else 0))
-        chunk = int(max_workspace_mb * (1 << 20)) // per_row
-        if chunk < 1:
-            raise ValueError(f"attention_saliency: max_workspace_mb={max_workspace_mb} is too small for one row ({per_row / (1 << 20):.1f} MB)")
+        chunk = self._gat_saliency_chunk("attention_saliency", N, through, max_workspace_mb)
         f32 = dict(dtype=torch.float32, device=dev)
         res = {"input_grad": torch.empty(nA, B, N, D, **f32), "hidden_grad": torch.empty(nA, B, N, A, **f32),
                "latent": torch.empty(nA, B, N, A, **f32)}
@@ -442,6 +448,180 @@ class Prediction_policy:
         res["active_h"], res["active_v"] = act_h, act_v
         res = {k: v.unflatten(1, (E, S)).permute(1, 2, 0, *range(3, v.dim() + 1)) for k, v in res.items()}
         return {k: v.cpu().numpy() for k, v in res.items()} if as_np else res
+
+    # ---------------------------------------------------------------------------- prediction saliency
+    def prediction_saliency(self, history_single, attention_hidden, behavior_latent=None, columns=(1, 2), horizons=None, target=None,
+                            noise=None, deterministic=True, social=None, gate="through", want=("summary",), presence_col=0,
+                            max_workspace_mb=256):
+        """What does the forecast of entity i at horizon step p depend on?  Inputs as ``predict``: history_single [E,nA,N,d],
+        attention_hidden [E,nA,N,A], behavior_latent [E,nA,N,Z] (needed with ``GAT_use_behavior``, ignored without).  The decoder
+        starts from the entity's own state x0 = history_single[.., i, :] and from the attention latent h0 = GAT(...)[i], the social
+        context; for every job (horizon step p, cotangent v on the prediction y_p) ``iplan_pdec_saliency`` returns d <v, y_p> / d x0
+        and d <v, y_p> / d h0 by BPTT through the autoregressive chain.
+        ``columns``: the output columns whose Jacobian rows are wanted (default: highway's position columns); ``horizons``: None =
+        all ``pred_length`` steps, an int, or a sorted list of distinct ints in [0, P).  ``target=None``: one one-hot job per
+        (horizon, column), horizon-major; a float tensor [E,nA,N,P,d]: one job per horizon with the row ``target[.., p, :]`` as
+        cotangent (``columns`` is ignored, the column axis has length 1).  ``deterministic=True`` runs the GAT without gumbel noise
+        (the gate is sigmoid((l1 - l0) / tau), as ``attention_map`` / ``attention_saliency`` do it) and draws nothing; otherwise
+        ``noise`` [nA,E,N,N-1,2] is used, or drawn from torch's generator as ``predict`` does.
+        Returns a dict, H = len(horizons), C = len(columns):
+          ``pred`` [E,nA,N,P,d]               the predictions, bit for bit ``predict``'s on the same noise
+          ``latent`` [E,nA,N,A]               h0, bit for bit ``GAT_latent_update``'s
+          ``state_l1``, ``latent_l1``, ``state_gxi``, ``latent_gxi`` [E,nA,N,H,C]   sum |G| and sum G x input over the columns of x0 / h0
+                                              ("summary" in ``want``)
+          ``state_grad`` [E,nA,N,H,C,d], ``latent_grad`` [E,nA,N,H,C,A]             the gradients ("grad" in ``want``)
+          ``horizon_l1`` float64 numpy [nA,H,2]   mean of (state_l1, latent_l1) over the present rows (column ``presence_col`` of x0
+                                              non-zero; < 0: every row) and over the columns -- own state against social context, per
+                                              horizon; NaN where nothing counts
+          ``active`` [E,nA,N,P,32] bool       the ReLU branches of the decoder's input layer ("act" in ``want``; tests)
+        ``social=(p, c)`` (p in ``horizons``, c in ``columns``; with a tensor ``target``: ``social=p``) continues that one job through
+        the GAT: the training-form GAT forward and ``iplan_gat_saliency`` with v_i = latent_grad[i, p, c, :] and the given ``gate``
+        ("through": exact, 1/tau included; "held": the gumbel gate is a constant), in ``attention_saliency``'s chunks under
+        ``max_workspace_mb`` (a row's bits do not depend on the chunking).  Adds ``pair_gl1``, ``pair_gxi`` [E,nA,N,N,n_src] (indexed
+        [ego i, entity j]) and ``input_grad`` [E,nA,N,d+Z]: the GAT path summed over the egos plus, on the history columns, the direct
+        path state_grad[j, p, c, :] of each entity's own row -- d sum_i y_{i,p,c} / d [history || behavior_latent]; hand its latent
+        columns to ``Behavior_policy.latent_saliency`` to reach the raw history.
+        numpy in -> numpy out, device tensors in -> device tensors out.  Parameters, gradients, optimiser state and (with
+        ``deterministic=True``) torch's generator are not touched.  Not covered: the teacher-forced and dropout forms of the decoder
+        (training only), second-order quantities, aggregation across data-parallel ranks."""
+        who = "prediction_saliency"
+        as_np = isinstance(history_single, np.ndarray)
+        dev = self.device
+        hist = _as_dev(history_single, dev)
+        if hist.dim() != 4:
+            raise ValueError(f"{who}: history_single must be [E,nA,N,d], got {tuple(hist.shape)}")
+        E, nA, N, d = hist.shape
+        A, P = self.args.attention_dim, self.pred_length
+        if nA != self.n_agents or d != self.obs_shape or not 2 <= N <= ops.L.GAT_MAX_ENTITIES:
+            raise ValueError(f"{who}: history_single {tuple(hist.shape)} does not fit n_agents={self.n_agents}, obs width {self.obs_shape}, "
+                             f"2 <= N <= {ops.L.GAT_MAX_ENTITIES}")
+        if P > ops.L.PDEC_SAL_MAX_P:
+            raise NotImplementedError(f"{who}: pred_length={P} exceeds IPLAN_PDEC_SAL_MAX_P={ops.L.PDEC_SAL_MAX_P}")
+        hid = _as_dev(attention_hidden, dev)
+        if hid.shape != (E, nA, N, A):
+            raise ValueError(f"{who}: attention_hidden {tuple(hid.shape)} != {(E, nA, N, A)}")
+        if gate not in ("through", "held"):
+            raise ValueError(f"{who}: gate={gate!r} is neither 'through' nor 'held'")
+        want = tuple(want)
+        if any(k not in ("summary", "grad", "act") for k in want):
+            raise ValueError(f"{who}: want={want} -- known: 'summary', 'grad', 'act'")
+        if deterministic and noise is not None:
+            raise ValueError(f"{who}: noise was given together with deterministic=True")
+        if not isinstance(presence_col, (int, np.integer)) or presence_col >= d:
+            raise ValueError(f"{who}: presence_col={presence_col!r} outside the {d} columns")
+        Z, lat = 0, None
+        if self.args.GAT_use_behavior:
+            if behavior_latent is None:
+                raise ValueError(f"{who}: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
+            lat = _as_dev(behavior_latent, dev)
+            Z = self.args.latent_dim
+            if lat.shape != (E, nA, N, Z):
+                raise ValueError(f"{who}: behavior_latent {tuple(lat.shape)} != {(E, nA, N, Z)}")
+            lat = lat.permute(1, 0, 2, 3).contiguous()
+        if noise is not None:
+            noise = _as_dev(noise, dev)
+            if noise.shape != (nA, E, N, N - 1, 2):
+                raise ValueError(f"{who}: noise {tuple(noise.shape)} != {(nA, E, N, N - 1, 2)}")
+            noise = noise.contiguous()
+
+        def ints(x, hi, what):
+            if isinstance(x, (int, np.integer)) and not isinstance(x, bool):
+                x = [x]
+            try:
+                x = list(x)
+            except TypeError:
+                raise ValueError(f"{who}: {what}={x!r} -- an int or a list of ints") from None
+            if not x or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < hi for i in x):
+                raise ValueError(f"{who}: {what}={x} -- ints in [0, {hi}), at least one")
+            return [int(i) for i in x]
+        hz = list(range(P)) if horizons is None else ints(horizons, P, "horizons")
+        if any(b <= a_ for a_, b in zip(hz, hz[1:])):
+            raise ValueError(f"{who}: horizons={hz} must be sorted and distinct")
+        vt = None
+        if target is None:
+            cols = ints(columns, d, "columns")
+            if len(set(cols)) != len(cols):
+                raise ValueError(f"{who}: columns={cols} must be distinct")
+            jobs = [(p, c) for p in hz for c in cols]
+        elif isinstance(target, (np.ndarray, torch.Tensor)) and target.ndim == 5:
+            vt = _as_dev(target, dev)
+            if vt.shape != (E, nA, N, P, d):
+                raise ValueError(f"{who}: target {tuple(vt.shape)} != {(E, nA, N, P, d)}")
+            vt = vt.permute(1, 0, 2, 3, 4).reshape(nA, E * N, P, d).contiguous()
+            cols = [None]
+            jobs = [(p, None) for p in hz]
+        else:
+            raise ValueError(f"{who}: target={target!r} -- None or a tensor [E,nA,N,P,d]")
+        H, C = len(hz), len(cols)
+        ks = None
+        if social is not None:
+            if vt is None:
+                ok = isinstance(social, (tuple, list)) and len(social) == 2 and all(isinstance(i, (int, np.integer)) for i in social)
+                if not ok or social[0] not in hz or social[1] not in cols:
+                    raise ValueError(f"{who}: social={social!r} -- a pair (p, c) with p in horizons={hz} and c in columns={cols}")
+                ks = hz.index(social[0]) * C + cols.index(social[1])
+            else:
+                if not isinstance(social, (int, np.integer)) or isinstance(social, bool) or social not in hz:
+                    raise ValueError(f"{who}: social={social!r} -- with a tensor target, one of horizons={hz}")
+                ks = hz.index(social)
+            through = gate == "through"
+            chunk = self._gat_saliency_chunk(who, N, through, max_workspace_mb)
+        f32 = dict(dtype=torch.float32, device=dev)
+        if hist.stride(3) != 1:
+            hist = hist.contiguous()
+        src0, hprev = hist.permute(1, 0, 2, 3), hid.permute(1, 0, 2, 3)
+        if deterministic:
+            nz = torch.zeros(nA, E, N, N - 1, 2, **f32)                            # l + 0 is exact: the gate of no noise
+        elif noise is not None:
+            nz = noise
+        else:
+            nz = gumbel_noise((nA, E, N, N - 1, 2), dev)
+        h0, _ = ops.gat_forward(self.gat_arena, src0, lat, hprev, nz)              # predict()'s launch: the rollout's bits
+        offset = (torch.arange(nA)[:, None] * hist.stride(1) + torch.arange(E)[None, :] * hist.stride(0)).to(torch.int64)
+        assert int(offset.max()) + (N - 1) * hist.stride(2) + d <= hist.untyped_storage().nbytes() // 4 - hist.storage_offset()
+        grads = "grad" in want or ks is not None
+        names = ("state_l1", "latent_l1", "pred") + (("state_gxi", "latent_gxi") if "summary" in want else ()) \
+            + (("state_grad", "latent_grad") if grads else ()) + (("active",) if "act" in want else ())
+        got = ops.pdec_saliency(self.dec_arena, hist, offset.to(dev), hist.stride(2), h0.reshape(nA, E * N, A), N, P, d, jobs, v=vt, want=names,
+                                checked=True)
+
+        def rows(t, *inner):                                                       # [nA, E*N, ...] -> [E, nA, N, ...]
+            return t.view(nA, E, N, *inner).permute(1, 0, 2, *range(3, 3 + len(inner)))
+        res = {"pred": rows(got["pred"], P, d), "latent": h0.permute(1, 0, 2, 3)}
+        per_job = {k: rows(got[k], H, C, *((d,) if k == "state_grad" else (A,) if k == "latent_grad" else ()))
+                   for k in names if k not in ("pred", "active")}
+        if "summary" in want:
+            res.update({k: per_job[k] for k in ("state_l1", "state_gxi", "latent_l1", "latent_gxi")})
+        if "grad" in want:
+            res.update(state_grad=per_job["state_grad"], latent_grad=per_job["latent_grad"])
+        if "act" in want:
+            bit = torch.arange(32, device=dev, dtype=torch.int32)
+            res["active"] = rows(((got["active"].unsqueeze(-1) >> bit) & 1).bool(), P, 32)
+        if ks is not None:
+            n_src, D = (2 if Z else 1), d + Z
+            pair_gl1, pair_gxi = torch.empty(nA, E, N, N, n_src, **f32), torch.empty(nA, E, N, N, n_src, **f32)
+            ig = torch.empty(nA, E, N, D, **f32)
+            v_gat = got["latent_grad"][:, :, ks].contiguous().view(nA, E, N, A)
+            outs = ("pair_gl1", "pair_gxi", "input_grad")
+            for b0 in range(0, E, chunk):
+                b1 = min(E, b0 + chunk)
+                # the record the backward reads: the training form of the same forward
+                _, saved = ops.gat_forward(self.gat_arena, src0[:, b0:b1], None if lat is None else lat[:, b0:b1], hprev[:, b0:b1],
+                                           nz[:, b0:b1].contiguous(), save=True)
+                ops.gat_saliency(self.gat_arena, saved, v_gat[:, b0:b1], gate_through=through, want=outs,
+                                 out={"pair_gl1": pair_gl1[:, b0:b1], "pair_gxi": pair_gxi[:, b0:b1], "input_grad": ig[:, b0:b1]})
+            ig[..., :d] += got["state_grad"][:, :, ks].view(nA, E, N, d)           # the direct path: each entity's own start state
+            res.update(pair_gl1=pair_gl1.permute(1, 0, 2, 3, 4), pair_gxi=pair_gxi.permute(1, 0, 2, 3, 4), input_grad=ig.permute(1, 0, 2, 3))
+        # own state against social context, per horizon: ONE host read-back
+        both = torch.stack([per_job["state_l1"], per_job["latent_l1"]], -1).cpu().numpy().astype(np.float64)      # [E, nA, N, H, C, 2]
+        present = (hist[..., presence_col] != 0).cpu().numpy() if presence_col >= 0 else np.ones((E, nA, N), dtype=bool)
+        count = present.sum(axis=(0, 2)).astype(np.float64) * C                   # [nA]
+        sums = np.where(present[:, :, :, None, None, None], both, 0.0).sum(axis=(0, 2, 4))      # [nA, H, 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            horizon_l1 = np.where(count[:, None, None] > 0, sums / count[:, None, None], np.nan)
+        res = {k: (t.cpu().numpy() if as_np else t) for k, t in res.items()}
+        res["horizon_l1"] = horizon_l1
+        return res
 
     # ---------------------------------------------------------------------------- learning
     def _sample(self, n_thread, avail_len):

@@ -1461,6 +1461,64 @@ def predict(arena, hist, offset, ent_stride, step_stride, h0, N, P, d, want_pred
     return out
 
 
+PDEC_SAL_OUTPUTS = ("state_grad", "latent_grad", "state_l1", "state_gxi", "latent_l1", "latent_gxi", "pred", "active")
+
+
+def pdec_saliency(arena, hist, offset, ent_stride, h0, N, P, d, jobs, v=None, want=("state_l1", "latent_l1"), out=None, checked=False, lib=None):
+    """d <v, y_p> / d x0 and / d h0 of the chain ``predict`` walks (csrc/pdec_saliency.hip), per row and job, for all nets.  ``hist``,
+    ``offset`` int64 [n_nets, S], ``ent_stride``, ``h0`` [n_nets, S*N, 32]: as ``predict`` (the start state is read in place).  ``jobs``:
+    K pairs (p, c) -- horizon step p in [0, P) and the output column c in [0, d) whose one-hot is the cotangent, or c = None / -1 for
+    the row ``v[net, row, p, :]`` of ``v`` [n_nets, S*N, P, d] (contiguous).  ``want``: names out of PDEC_SAL_OUTPUTS.  Returns a dict
+    with state_grad [n_nets, S*N, K, d], latent_grad [n_nets, S*N, K, 32], state_l1 / state_gxi / latent_l1 / latent_gxi [n_nets, S*N, K],
+    pred [n_nets, S*N, P, d], active int32 [n_nets, S*N, P] (a 32-bit mask), None for what was not asked for.  ``out``: optional dict of
+    destination tensors of exactly those shapes (contiguous) for some of the wanted names.  Unless ``checked`` the offsets are read
+    back and checked against hist's storage."""
+    lib = _lib(lib)
+    n_nets, S = offset.shape
+    dev = h0.device
+    want = tuple(want)
+    assert all(k in PDEC_SAL_OUTPUTS for k in want), want
+    assert offset.dtype == torch.int64 and offset.is_contiguous() and offset.device == dev
+    assert hist.dtype == torch.float32 and hist.device == dev
+    assert h0.shape == (n_nets, S * N, 32) and h0.is_contiguous() and h0.dtype == torch.float32
+    assert ent_stride >= 0
+    if not checked:
+        lo, hi = int(offset.min()), int(offset.max())
+        assert lo >= 0, ("start rows outside hist", lo)
+        _inside(hist, hi + (N - 1) * ent_stride + d, "pdec_saliency: hist")
+    jobs = [(int(p), -1 if c is None else int(c)) for p, c in jobs]
+    K, rows = len(jobs), S * N
+    a = L.PdecSaliencyArgs()
+    a.n_nets, a.S, a.N, a.P, a.d, a.K = n_nets, S, N, P, d, K
+    a.x0, a.offset, a.ent_stride, a.h0 = hist.data_ptr(), offset.data_ptr(), ent_stride, h0.data_ptr()
+    a.params, a.params_s_net = arena.data.data_ptr(), arena.net_stride
+    for i, k in enumerate(L.DEC_PARAM_ORDER):
+        a.off[i] = arena.off(k)
+    flat = [x for job in jobs for x in job]
+    j_host = (C.c_int32 * max(2 * K, 2))(*flat)
+    j_dev = torch.tensor(flat, dtype=torch.int32, device=dev) if K else None
+    a.jobs, a.jobs_host = L.ptr(j_dev), C.cast(j_host, C.c_void_p)
+    if v is not None:
+        assert v.dtype == torch.float32 and v.device == dev and v.is_contiguous() and v.shape == (n_nets, rows, P, d), v.shape
+        a.v = v.data_ptr()
+    shapes = dict(state_grad=(K, d), latent_grad=(K, 32), state_l1=(K,), state_gxi=(K,), latent_l1=(K,), latent_gxi=(K,), pred=(P, d), active=(P,))
+    res = {k: None for k in PDEC_SAL_OUTPUTS}
+    for k in want:
+        shape = (n_nets, rows) + shapes[k]
+        dt = torch.int32 if k == "active" else torch.float32
+        if out is not None and k in out:
+            t = out[k]
+            assert t.shape == shape and t.dtype == dt and t.is_contiguous() and t.device == dev, (k, t.shape, shape)
+        else:
+            t = torch.empty(shape, dtype=dt, device=dev)
+        res[k] = t
+        setattr(a, k, t.data_ptr())
+    _launch("pdec_sal_kernel", lambda: lib.call("iplan_pdec_saliency", a, L.current_stream(dev)))
+    res["_args"] = a
+    res["_keep"] = (hist, offset, h0, j_host, j_dev, v)
+    return res
+
+
 # ---- behaviour learning ---------------------------------------------------------------------------------
 def _beh_pieces(which, default):
     """Window pieces of the behaviour forward / backward pipelines (IPLAN_BEH_PIECES[_FWD|_BWD]: tuning / test knobs)."""
