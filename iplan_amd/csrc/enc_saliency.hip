@@ -12,73 +12,24 @@
 //          dh  = z dh + W_hh^T [dr | dz | r dn],      dx_s = W_lin^T (relu' . W_ih^T [dr | dz | dn])
 //      A step is read by up to L windows; windows are walked downwards, so step s is complete once window w = s has been walked:
 //      at most L rows are pending at a time (a ring in LDS), and a finished row is reduced to its outputs and written once.
-// All weights sit in LDS in BOTH orientations, staged once per workgroup (70 KB); the slab and the ring are lane-private (every lane
-// reads back only what it wrote: D layout in, D layout out), so a wave never waits for another.  The number of waves per workgroup
-// follows from L (3 KB per step and wave).  No atomics, no cross-chain sums: the MFMA keeps chains in separate columns, so a slot's
-// bits do not depend on its lane, tile, workgroup or on the other target windows.
-#include "api_util.h"
-#include "gru_tile.h"
+// The chain's steps in both directions, the weights in LDS and the lane-private slab (here: the entering states and the ring) are
+// chain_sal.h's, shared with pdec_saliency.hip; the number of waves per workgroup follows from L.  No atomics, no cross-chain sums: the
+// MFMA keeps chains in separate columns, so a slot's bits do not depend on its lane, tile, workgroup or on the other target windows.
+#include "chain_sal.h"
 
 namespace iplan {
 
-constexpr int SE = 32, SET = 2, SELD = SE + 8;     // encoder_rnn_dim; leading dims: ld % 16 == 8 -> conflict-free fragment reads
-constexpr int SLLD = 24;                           // leading dim of [.. x 16] matrices (d, Z <= 16 real columns)
-constexpr int SGLD = 3 * SE + 8;                   // leading dim of the transposed GRU weights [32 x 96]
-constexpr int S_LIN = 0;                           // W_lin   [32 x d]
-constexpr int S_LINT = S_LIN + SE * SLLD;          // W_lin^T [16 x 32]
-constexpr int S_WIH = S_LINT + 16 * SELD;          // W_ih    [96 x 32]
-constexpr int S_WHH = S_WIH + 3 * SE * SELD;       // W_hh    [96 x 32]
-constexpr int S_WIHT = S_WHH + 3 * SE * SELD;      // W_ih^T  [32 x 96]
-constexpr int S_WHHT = S_WIHT + SE * SGLD;         // W_hh^T  [32 x 96]
-constexpr int S_OUT = S_WHHT + SE * SGLD;          // W_out   [Z x 32]
-constexpr int S_OUTT = S_OUT + 16 * SELD;          // W_out^T [32 x Z]
-constexpr int S_B = S_OUTT + SE * SLLD;            // biases: linear 0 (32) | b_ih 32 (96) | b_hh 128 (96) | out 224 (16)
-constexpr int S_W_FLOATS = S_B + SE + 6 * SE + 16;
-constexpr int S_LDS_FLOATS = 160 * 1024 / 4;
-constexpr int S_STEP_FLOATS = 16 * SE + 16 * 16;   // per wave and window step: one entering state and one pending row of 16 chains
-static_assert(S_W_FLOATS % 4 == 0 && S_B % 4 == 0 && S_LINT % 4 == 0 && S_OUTT % 4 == 0, "16-byte aligned fragments");
-static_assert(S_W_FLOATS + IPLAN_ENC_SAL_MAX_L * S_STEP_FLOATS <= S_LDS_FLOATS, "one wave's slab and ring must fit beside the weights");
+static_assert(chain_fits(IPLAN_ENC_SAL_MAX_L), "one wave's slab and ring must fit beside the weights");
+static_assert(!chain_fits(IPLAN_ENC_SAL_MAX_L + 1), "IPLAN_ENC_SAL_MAX_L is what the LDS budget admits");
 
-inline int enc_sal_waves(int L) { return imin(4, (S_LDS_FLOATS - S_W_FLOATS) / (L * S_STEP_FLOATS)); }
-
-__device__ __forceinline__ void enc_sal_stage(float* lds, const IplanEncSaliencyArgs& a, int net) {
-    const float* __restrict__ P = a.enc_params + (int64_t)net * a.enc_s_net;
-    stage_matrix(lds + S_LIN, SLLD, SE, P + a.enc_off[IPLAN_ENC_LIN_W], SE, a.d);
-    stage_matrix_t(lds + S_LINT, SELD, 16, P + a.enc_off[IPLAN_ENC_LIN_W], SE, a.d);
-    stage_matrix(lds + S_WIH, SELD, 3 * SE, P + a.enc_off[IPLAN_ENC_WIH], 3 * SE, SE);
-    stage_matrix(lds + S_WHH, SELD, 3 * SE, P + a.enc_off[IPLAN_ENC_WHH], 3 * SE, SE);
-    stage_matrix_t(lds + S_WIHT, SGLD, SE, P + a.enc_off[IPLAN_ENC_WIH], 3 * SE, SE);
-    stage_matrix_t(lds + S_WHHT, SGLD, SE, P + a.enc_off[IPLAN_ENC_WHH], 3 * SE, SE);
-    stage_matrix(lds + S_OUT, SELD, 16, P + a.enc_off[IPLAN_ENC_OUT_W], a.Z, SE);
-    stage_matrix_t(lds + S_OUTT, SLLD, SE, P + a.enc_off[IPLAN_ENC_OUT_W], a.Z, SE);
-    stage_vector(lds + S_B, SE, P + a.enc_off[IPLAN_ENC_LIN_B], SE);
-    stage_vector(lds + S_B + 32, 3 * SE, P + a.enc_off[IPLAN_ENC_BIH], 3 * SE);
-    stage_vector(lds + S_B + 128, 3 * SE, P + a.enc_off[IPLAN_ENC_BHH], 3 * SE);
-    stage_vector(lds + S_B + 224, 16, P + a.enc_off[IPLAN_ENC_OUT_B], a.Z);
-}
-
-// columns 4g .. 4g+3 of step `st` of a chain's history, zero past column d and for the zero padding st < 0 (the loads are clamped
-// to the row and masked bitwise: a NaN in a step or column that is not the chain's own input never enters the arithmetic)
+// columns 4g .. 4g+3 of step `st` of a chain's history, zero past column d and for the zero padding st < 0
 __device__ __forceinline__ f32x4 enc_sal_x(const float* __restrict__ hrow, int64_t s_t, int st, int d, int g) {
-    const IPLAN_GLOBAL_AS float* p = as_global(hrow + (int64_t)(st < 0 ? 0 : st) * s_t);
-    f32x4 v;
-    for (int q = 0; q < 4; ++q) {
-        const int i = 4 * g + q;
-        v[q] = keep_if(st >= 0 && i < d, p[i < d ? i : d - 1]);
-    }
-    return v;
-}
-
-// one chain step: u = ReLU(W_lin x + b_lin), h = GRU32(u, h); `keep`: the gate activations for the backward pass
-__device__ __forceinline__ void enc_sal_step(const float* lds, f32x4 x, f32x4 (&u)[SET], f32x4 (&h)[SET], GruGates* keep) {
-    const f32x4 xin[1] = {x};
-    for (int T = 0; T < SET; ++T) u[T] = relu4(dense_tile<1>(lds + S_LIN, SLLD, 16 * T, xin, bfrag_lds(lds + S_B, T)));
-    gru_step_lds<SET, SET>(lds + S_WIH, SELD, lds + S_WHH, SELD, lds + S_B + 32, lds + S_B + 128, u, h, keep);
+    return chain_row_load(hrow + (int64_t)(st < 0 ? 0 : st) * s_t, st >= 0, d, g);
 }
 
 // p = softmax(W_out h + b_out) over the Z real columns (0 elsewhere), as beh_eval_kernel forms it
-__device__ __forceinline__ f32x4 enc_sal_softmax(const float* lds, const f32x4 (&h)[SET], int Z, int g) {
-    const f32x4 lg = dense_tile<SET>(lds + S_OUT, SELD, 0, h, bfrag_lds(lds + S_B + 224, 0));
+__device__ __forceinline__ f32x4 enc_sal_softmax(const float* lds, const f32x4 (&h)[CHT], int Z, int g) {
+    const f32x4 lg = dense_tile<CHT>(lds + C_OUT, CHLD, 0, h, bfrag_lds(lds + C_BOUT, 0));
     float mx = -INFINITY;
     for (int q = 0; q < 4; ++q)
         if (4 * g + q < Z) mx = fmaxf(mx, lg[q]);
@@ -117,7 +68,7 @@ __device__ __forceinline__ f32x4 enc_sal_softmax_bwd(f32x4 p, f32x4 gv) {
 __global__ __launch_bounds__(256) void enc_sal_fwd_kernel(IplanEncSaliencyArgs a, int Jn) {
     IPLAN_DYN_LDS(lds);
     const int net = (int)blockIdx.y;
-    enc_sal_stage(lds, a, net);
+    chain_stage(lds, a.enc_params + (int64_t)net * a.enc_s_net, a.enc_off, a.d, a.Z);
     __syncthreads();
     const int l = lane_id(), n = l & 15, g = l >> 4;
     const int rows = a.E * a.N;
@@ -132,21 +83,21 @@ __global__ __launch_bounds__(256) void enc_sal_fwd_kernel(IplanEncSaliencyArgs a
     const float* __restrict__ hrow = a.hist + (int64_t)net * a.h_s_net + (int64_t)e * a.h_s_e + (int64_t)ent * d;
     const int64_t gr = (int64_t)net * rows + rc;
     float* __restrict__ he_all = a.scratch;
-    int32_t* __restrict__ tix = reinterpret_cast<int32_t*>(a.scratch + (int64_t)a.n_nets * rows * Jn * SE);
+    int32_t* __restrict__ tix = reinterpret_cast<int32_t*>(a.scratch + (int64_t)a.n_nets * rows * Jn * CH);
 
-    f32x4 h[SET], lat = splat4(0.f);
-    for (int T = 0; T < SET; ++T) h[T] = splat4(0.f);
+    f32x4 h[CHT], lat = splat4(0.f);
+    for (int T = 0; T < CHT; ++T) h[T] = splat4(0.f);
     int wi = 0;
     for (int j = 0; j < Jn; ++j) {
         for (int t = 0; t < L; ++t) {
-            f32x4 u[SET];
-            enc_sal_step(lds, enc_sal_x(hrow, a.h_s_t, j - (L - 1) + t, d, g), u, h, nullptr);
+            f32x4 u[CHT];
+            chain_step(lds, enc_sal_x(hrow, a.h_s_t, j - (L - 1) + t, d, g), u, h, nullptr);
         }
-        for (int T = 0; T < SET; ++T) vstore_a(he_all + (gr * Jn + j) * SE, valid, T, h[T]);
+        for (int T = 0; T < CHT; ++T) vstore_a(he_all + (gr * Jn + j) * CH, valid, T, h[T]);
         const f32x4 p = enc_sal_softmax(lds, h, Z, g);
         for (int q = 0; q < 4; ++q) lat[q] = (1.0f - a.coef) * lat[q] + p[q] * a.coef;
         if (wi < nW && a.windows[wi] == j) {
-            if (a.latent) {
+            if (a.latent) {                  // (not chain_row_store: with it the loops above land elsewhere and the call takes 0.3 % longer)
                 float* lrow = a.latent + (gr * nW + wi) * Z;
                 for (int q = 0; q < 4; ++q)
                     if (valid && 4 * g + q < Z) lrow[4 * g + q] = lat[q];
@@ -177,7 +128,7 @@ __global__ __launch_bounds__(256) void enc_sal_fwd_kernel(IplanEncSaliencyArgs a
 __global__ __launch_bounds__(256) void enc_sal_bwd_kernel(IplanEncSaliencyArgs a, int Jn, int wpb) {
     IPLAN_DYN_LDS(lds);
     const int net = (int)blockIdx.y;
-    enc_sal_stage(lds, a, net);
+    chain_stage(lds, a.enc_params + (int64_t)net * a.enc_s_net, a.enc_off, a.d, a.Z);
     __syncthreads();
     const int l = lane_id(), n = l & 15, g = l >> 4;
     const int rows = a.E * a.N;
@@ -194,11 +145,11 @@ __global__ __launch_bounds__(256) void enc_sal_bwd_kernel(IplanEncSaliencyArgs a
     const int64_t gr = (int64_t)net * rows + rc;
     const int64_t slot = gr * nW + wi;
     const float* __restrict__ he_all = a.scratch;
-    const int32_t* __restrict__ tix = reinterpret_cast<const int32_t*>(a.scratch + (int64_t)a.n_nets * rows * Jn * SE);
+    const int32_t* __restrict__ tix = reinterpret_cast<const int32_t*>(a.scratch + (int64_t)a.n_nets * rows * Jn * CH);
     // lane-private LDS: entering states hs[t][T] and the ring of pending rows, one f32x4 per lane each
-    float* slab = lds + S_W_FLOATS + wave_id() * L * S_STEP_FLOATS;
-    f32x4* hs = reinterpret_cast<f32x4*>(slab) + l;                     // hs[(t * SET + T) * 64]
-    f32x4* ring = reinterpret_cast<f32x4*>(slab + L * 16 * SE) + l;     // ring[(s % L) * 64]
+    float* slab = lds + C_W_FLOATS + wave_id() * L * C_STEP_FLOATS;
+    f32x4* hs = reinterpret_cast<f32x4*>(slab) + l;                     // hs[(t * CHT + T) * 64]
+    f32x4* ring = reinterpret_cast<f32x4*>(slab + L * 16 * CH) + l;     // ring[(s % L) * 64]
 
     const int j = a.windows[wi];
     const int Kj = imin(K, j), w0 = j - Kj;
@@ -211,8 +162,8 @@ __global__ __launch_bounds__(256) void enc_sal_bwd_kernel(IplanEncSaliencyArgs a
         for (int q = 0; q < 4; ++q) v[q] = 4 * g + q == pick ? 1.f : 0.f;
     }
     for (int t = 0; t < L; ++t) ring[t * 64] = splat4(0.f);
-    f32x4 dh[SET], feat = splat4(0.f);
-    for (int T = 0; T < SET; ++T) dh[T] = splat4(0.f);
+    f32x4 dh[CHT], feat = splat4(0.f);
+    for (int T = 0; T < CHT; ++T) dh[T] = splat4(0.f);
     float sc = a.coef;                                                  // c (1 - c)^(j - w)
 
     // a finished row: G[r] of step s = j - r >= 0, reduced to the outputs
@@ -226,11 +177,7 @@ __global__ __launch_bounds__(256) void enc_sal_bwd_kernel(IplanEncSaliencyArgs a
         }
         l1 = group_sum(l1);
         gx = group_sum(gx);
-        if (a.grad) {
-            float* grow = a.grad + (slot * R + r) * d;
-            for (int q = 0; q < 4; ++q)
-                if (valid && 4 * g + q < d) grow[4 * g + q] = G[q];
-        }
+        if (a.grad) chain_row_store(a.grad + (slot * R + r) * d, valid, d, g, G);
         if (valid && g == 0) {
             if (a.step_l1) a.step_l1[slot * R + r] = l1;
             if (a.step_gxi) a.step_gxi[slot * R + r] = gx;
@@ -239,51 +186,31 @@ __global__ __launch_bounds__(256) void enc_sal_bwd_kernel(IplanEncSaliencyArgs a
 
     for (int w = j; w >= w0; --w) {
         // restart window w from he_{w-1}
-        f32x4 h[SET];
-        for (int T = 0; T < SET; ++T) h[T] = w > 0 ? vload_a(he_all + (gr * Jn + (w - 1)) * SE, true, T) : splat4(0.f);
+        f32x4 h[CHT];
+        for (int T = 0; T < CHT; ++T) h[T] = w > 0 ? vload_a(he_all + (gr * Jn + (w - 1)) * CH, true, T) : splat4(0.f);
         for (int t = 0; t < L; ++t) {
-            for (int T = 0; T < SET; ++T) hs[(t * SET + T) * 64] = h[T];
-            f32x4 u[SET];
-            enc_sal_step(lds, enc_sal_x(hrow, a.h_s_t, w - (L - 1) + t, d, g), u, h, nullptr);
+            for (int T = 0; T < CHT; ++T) hs[(t * CHT + T) * 64] = h[T];
+            f32x4 u[CHT];
+            chain_step(lds, enc_sal_x(hrow, a.h_s_t, w - (L - 1) + t, d, g), u, h, nullptr);
         }
         // the window's share of lat_j: c (1 - c)^(j - w) p_w
         {
             const f32x4 p = enc_sal_softmax(lds, h, Z, g);
             const f32x4 dl[1] = {enc_sal_softmax_bwd(p, v * sc)};
-            for (int T = 0; T < SET; ++T) dh[T] = dense_tile<1>(lds + S_OUTT, SLLD, 16 * T, dl, dh[T]);
+            for (int T = 0; T < CHT; ++T) dh[T] = dense_tile<1>(lds + C_OUTT, CLLD, 16 * T, dl, dh[T]);
         }
         for (int t = L - 1; t >= 0; --t) {
             const int s = w - (L - 1) + t;
-            f32x4 hp[SET], ht[SET], u[SET];
-            for (int T = 0; T < SET; ++T) ht[T] = hp[T] = hs[(t * SET + T) * 64];
-            GruGates keep[SET];
-            enc_sal_step(lds, enc_sal_x(hrow, a.h_s_t, s, d, g), u, ht, keep);
-            f32x4 di[3 * SET], dg[3 * SET], direct[SET];
-            for (int T = 0; T < SET; ++T) {
-                const GruGrads o = gru_gates_bwd(dh[T], keep[T].r, keep[T].z, keep[T].n, keep[T].hn, hp[T]);
-                di[T] = dg[T] = o.dr;
-                di[SET + T] = dg[SET + T] = o.dz;
-                di[2 * SET + T] = o.dni;
-                dg[2 * SET + T] = o.dnh;
-                direct[T] = o.dh_direct;
-            }
-            f32x4 du[SET];
-            uint32_t bits = 0;
-            for (int T = 0; T < SET; ++T) {
-                du[T] = dense_tile<3 * SET>(lds + S_WIHT, SGLD, 16 * T, di, splat4(0.f));
-                dh[T] = dense_tile<3 * SET>(lds + S_WHHT, SGLD, 16 * T, dg, direct[T]);
-                for (int q = 0; q < 4; ++q) {
-                    const bool on = u[T][q] > 0.0f;
-                    du[T][q] = on ? du[T][q] : 0.0f;
-                    bits |= on ? 1u << (16 * T + 4 * g + q) : 0u;
-                }
-            }
-            if (s >= 0) ring[(s % L) * 64] += dense_tile<SET>(lds + S_LINT, SELD, 0, du, splat4(0.f));
+            f32x4 hp[CHT], ht[CHT], u[CHT];
+            for (int T = 0; T < CHT; ++T) ht[T] = hp[T] = hs[(t * CHT + T) * 64];
+            GruGates keep[CHT];
+            chain_step(lds, enc_sal_x(hrow, a.h_s_t, s, d, g), u, ht, keep);
+            uint32_t bits;
+            const f32x4 dx = chain_step_bwd(lds, keep, hp, u, dh, g, &bits);
+            if (s >= 0) ring[(s % L) * 64] += dx;
             if (a.active) {
-                int b = (int)bits;
-                b |= __shfl_xor(b, 16);
-                b |= __shfl_xor(b, 32);
-                if (valid && g == 0) a.active[(slot * (K + 1) + (j - w)) * L + t] = (uint32_t)b;
+                const uint32_t b = chain_row_or(bits);
+                if (valid && g == 0) a.active[(slot * (K + 1) + (j - w)) * L + t] = b;
             }
         }
         emit(j - w, ring[(w % L) * 64]);                                 // no later window reads step w
@@ -294,11 +221,7 @@ __global__ __launch_bounds__(256) void enc_sal_bwd_kernel(IplanEncSaliencyArgs a
     for (int s = w0 - 1; s >= s_lo; --s) emit(j - s, ring[(s % L) * 64]);
     // rows beyond the truncation and rows of the zero padding: exactly 0
     for (int r = j - s_lo + 1; r < R; ++r) {
-        if (a.grad) {
-            float* grow = a.grad + (slot * R + r) * d;
-            for (int q = 0; q < 4; ++q)
-                if (valid && 4 * g + q < d) grow[4 * g + q] = 0.f;
-        }
+        if (a.grad) chain_row_store(a.grad + (slot * R + r) * d, valid, d, g, splat4(0.f));
         if (valid && g == 0) {
             if (a.step_l1) a.step_l1[slot * R + r] = 0.f;
             if (a.step_gxi) a.step_gxi[slot * R + r] = 0.f;
@@ -307,14 +230,10 @@ __global__ __launch_bounds__(256) void enc_sal_bwd_kernel(IplanEncSaliencyArgs a
     if (a.active && valid && g == 0)
         for (int k = Kj + 1; k <= K; ++k)
             for (int t = 0; t < L; ++t) a.active[(slot * (K + 1) + k) * L + t] = 0u;
-    if (a.feature_l1) {
-        float* frow = a.feature_l1 + slot * d;
-        for (int q = 0; q < 4; ++q)
-            if (valid && 4 * g + q < d) frow[4 * g + q] = feat[q];
-    }
+    if (a.feature_l1) chain_row_store(a.feature_l1 + slot * d, valid, d, g, feat);
     if (a.carry_l2) {
         float sq = 0.f;
-        for (int T = 0; T < SET; ++T)
+        for (int T = 0; T < CHT; ++T)
             for (int q = 0; q < 4; ++q) sq = fmaf(dh[T][q], dh[T][q], sq);
         sq = group_sum(sq);
         if (valid && g == 0) a.carry_l2[slot] = w0 > 0 ? sqrtf(sq) : 0.f;      // he_{-1} = 0 is a constant, not a state
@@ -346,22 +265,22 @@ extern "C" int iplan_enc_saliency(const IplanEncSaliencyArgs* a, iplan_stream_t 
     if (!bwd && !a->latent && !a->target_index) return fail(IPLAN_EINVAL, "iplan_enc_saliency: no output asked for");
     const int rows = a->E * a->N, tiles = (rows + 15) / 16;
     const int Jn = a->windows_host[a->nW - 1] + 1;
-    const int64_t need = (int64_t)a->n_nets * rows * Jn * SE + (int64_t)a->n_nets * rows * a->nW;
+    const int64_t need = (int64_t)a->n_nets * rows * Jn * CH + (int64_t)a->n_nets * rows * a->nW;
     if (a->scratch_floats < need)
         return fail(IPLAN_EINVAL, "iplan_enc_saliency: scratch_floats=%lld, %lld are needed", (long long)a->scratch_floats, (long long)need);
     if ((int64_t)tiles * a->nW > 0x7fffffff - 4 || (int64_t)a->n_nets * rows * a->nW > 0x7fffffff / 16)
         return fail(IPLAN_EINVAL, "iplan_enc_saliency: %d tiles x %d windows are too many for one launch", tiles, a->nW);
     if (!aligned16(a->scratch)) return fail(IPLAN_EALIGN, "iplan_enc_saliency: scratch must be 16-byte aligned");
     {
-        const size_t lds = sizeof(float) * S_W_FLOATS;
+        const size_t lds = sizeof(float) * C_W_FLOATS;
 #ifndef IPLAN_HOST_EMULATION
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(enc_sal_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 #endif
         hipLaunchKernelGGL(enc_sal_fwd_kernel, dim3((unsigned)((tiles + 3) / 4), (unsigned)a->n_nets), dim3(256), lds, (hipStream_t)stream, *a, Jn);
     }
     if (bwd) {
-        const int wpb = enc_sal_waves(a->L);
-        const size_t lds = sizeof(float) * (S_W_FLOATS + (size_t)wpb * a->L * S_STEP_FLOATS);
+        const int wpb = chain_waves(a->L);
+        const size_t lds = sizeof(float) * (C_W_FLOATS + (size_t)wpb * a->L * C_STEP_FLOATS);
         const int tasks = tiles * a->nW;
 #ifndef IPLAN_HOST_EMULATION
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(enc_sal_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
