@@ -11,6 +11,7 @@ Same constructor and method contracts as the reference.  Differences are interna
     (plain tensor plumbing) for callers that want the assembled tensor.
 """
 import copy
+from types import SimpleNamespace
 
 import numpy as np
 import torch as th
@@ -19,6 +20,11 @@ from .. import ops
 from ..arena import ParamArena
 from ..modules.agents.ippo_actor import R_Actor
 from ..modules.critics.ippo_critic import R_Critic
+
+
+def _esn(t):
+    """(net, chain, step) strides of a [E, S, nA, ...] tensor"""
+    return (t.stride(2), t.stride(0), t.stride(1))
 
 
 class DcntrlMAC:
@@ -127,49 +133,74 @@ class DcntrlMAC:
     # ------------------------------------------------------------------------------ inspection
     POLICY_STATS = ("weight", "entropy", "greedy_is_recorded", "logp", "value", "max_prob")
 
-    def _trace(self, batch, t0, S, hidden0, which, want, want_h):
-        """ops.policy_trace over steps t0 .. t0 + S - 1 of ``batch``, fields read in place -> ([nA, E, S, ..] results, as_numpy)"""
+    def _rows(self, batch, t0, S):
+        """The rows the policy saw at steps t0 .. t0 + S - 1 of a recorded ``batch`` (fields [E, T1, nA, ...], torch or numpy), read
+        in place: the feature spec (row (e, s) at physical row e * T1 + t0 + s; the last action is the recorded one of t - 1, none
+        at t = 0), the int32 ``avail`` and int64 ``acts`` [E, S, nA] of those steps, the packed fc1 operands, and the accessors
+        ``dev`` (anything -> this device) and ``field`` (a batch field, each fetched once)."""
         a = self.args
-        if a.layer_N != 1 or a.recurrent_N != 1:
-            raise NotImplementedError("policy_trace / action_distribution cover layer_N = recurrent_N = 1 only")
-        nA, N, M = self.n_agents, a.max_vehicle_num, a.rnn_hidden_dim
-        as_np = isinstance(batch["history"], np.ndarray)
+        fields = {}
+
+        def dev(t, dtype=None):
+            return self._dev(th.as_tensor(t), dtype)
 
         def field(key, dtype=None):
             """[E, T1, ...] on the device, rows addressable as e * T1 + t (a copy only when the batch's layout is not that)"""
-            t = batch[key]
-            t = self._dev(th.as_tensor(t) if isinstance(t, np.ndarray) else t, dtype)
-            return t if t.stride(0) == t.shape[1] * t.stride(1) and t[0, 0].is_contiguous() else t.contiguous()
+            if (key, dtype) not in fields:
+                t = dev(batch[key], dtype)
+                fields[key, dtype] = t if t.stride(0) == t.shape[1] * t.stride(1) and t[0, 0].is_contiguous() else t.contiguous()
+            return fields[key, dtype]
 
         hist = field("history", th.float32)
         E, T1 = hist.shape[:2]
-        assert 0 <= t0 and t0 + S <= T1 and S >= 1, (t0, S, T1)
+        assert 0 <= t0 and S >= 1 and t0 + S <= T1, (t0, S, T1)
+        sl = slice(t0, t0 + S)
         sources = []
         for key, w in self._widths():
-            view = (hist if key == "history" else field(key, th.float32))[:, t0:t0 + S]          # [E, S, nA, N, w]
+            view = (hist if key == "history" else field(key, th.float32))[:, sl]                  # [E, S, nA, N, w]
             sources.append((view, w, view.stride(2), view.stride(1)))
-        acts = field("actions")[..., 0]                                                       # [E, T1, nA] int64
+        acts = field("actions")[..., 0]                                                           # [E, T1, nA] int64
         last, la_strides = None, (0, 0)
         if a.obs_last_action:
-            last = th.cat([th.full_like(acts[:, :1], -1), acts[:, :-1]], 1)[:, t0:t0 + S]     # the action of t - 1; none at t = 0
+            last = th.cat([th.full_like(acts[:, :1], -1), acts[:, :-1]], 1)[:, sl]                # the action of t - 1; none at t = 0
             la_strides = (last.stride(2), last.stride(1))
-        spec = ops.AcFeatureSpec(N, sources, n_actions=a.n_actions if a.obs_last_action else 0, last_action=last, la_strides=la_strides,
-                                 n_id=nA if a.obs_agent_id else 0, T=S, T_phys=T1)
+        spec = ops.AcFeatureSpec(a.max_vehicle_num, sources, n_actions=a.n_actions if a.obs_last_action else 0, last_action=last,
+                                 la_strides=la_strides, n_id=self.n_agents if a.obs_agent_id else 0, T=S, T_phys=T1)
         assert spec.F == self.input_shape, (spec.F, self.input_shape)
         avail = field("avail_actions")
         if avail.dtype != th.int32:
             avail = avail.to(th.int32)
-        avail = avail[:, t0:t0 + S]
-        acts = acts[:, t0:t0 + S]
+        return SimpleNamespace(spec=spec, E=E, T1=T1, sl=sl, avail=avail[:, sl], acts=acts[:, sl], dev=dev, field=field,
+                               as_np=isinstance(batch["history"], np.ndarray), packed=self.fc1_pack.get(spec))
+
+    def _target(self, r, target):
+        """``target`` of saliency / saliency_trace -> (a* per row, int64 [E, S, nA], or None = every row's greedy action; its strides)"""
+        if isinstance(target, str):
+            assert target in ("recorded", "greedy"), target
+            tgt = r.acts if target == "recorded" else None
+        else:
+            tgt = r.dev(target, th.int64)
+            assert tgt.shape == r.acts.shape, (tgt.shape, tuple(r.acts.shape))
+        return tgt, _esn(tgt) if tgt is not None else (0, 0, 0)
+
+    def _trace(self, batch, t0, S, hidden0, which, want, want_h, rows=None):
+        """ops.policy_trace over steps t0 .. t0 + S - 1 of ``batch``, fields read in place -> ([nA, E, S, ..] results, as_numpy,
+        the recorded actions); ``rows``: ``_rows(batch, t0, S)`` where the caller has it already"""
+        a = self.args
+        if a.layer_N != 1 or a.recurrent_N != 1:
+            raise NotImplementedError("policy_trace / action_distribution cover layer_N = recurrent_N = 1 only")
+        nA, M = self.n_agents, a.rnn_hidden_dim
+        r = rows if rows is not None else self._rows(batch, t0, S)
+        E, avail, acts = r.E, r.avail, r.acts
         if isinstance(hidden0, str):
             assert hidden0 == "zeros", hidden0
             ha = hc = None
             hs = (0, 0)
         else:
             if hidden0 is None:
-                ha, hc = field("rnn_states_actors", th.float32)[:, t0], field("rnn_states_critics", th.float32)[:, t0]
+                ha, hc = r.field("rnn_states_actors", th.float32)[:, t0], r.field("rnn_states_critics", th.float32)[:, t0]
             else:
-                ha, hc = (self._dev(th.as_tensor(h), th.float32) for h in hidden0)
+                ha, hc = (r.dev(h, th.float32) for h in hidden0)
             assert ha.shape == hc.shape == (E, nA, M), (ha.shape, hc.shape)
             if ha.stride() != hc.stride() or ha.stride(2) != 1:
                 ha, hc = ha.contiguous(), hc.contiguous()
@@ -178,11 +209,11 @@ class DcntrlMAC:
         want = tuple(k for k in want if (k == "values" and w != 0) or (k != "values" and w != 1))
         if want_h:
             want += tuple(k for k, on in (("h_actor", w != 1), ("h_critic", w != 0)) if on)
-        res = ops.policy_trace(self.actor_arena, self.critic_arena, w, spec, E, S, nA, hidden0_actor=ha, hidden0_critic=hc, h_strides=hs,
+        res = ops.policy_trace(self.actor_arena, self.critic_arena, w, r.spec, E, S, nA, hidden0_actor=ha, hidden0_critic=hc, h_strides=hs,
                                avail=avail, avail_strides=(avail.stride(2), avail.stride(1)),
                                actions_in=acts if "logp" in want else None, act_strides=(acts.stride(2), acts.stride(1)),
-                               n_actions=a.n_actions, want=want, packed=self.fc1_pack.get(spec))
-        return res, as_np, acts
+                               n_actions=a.n_actions, want=want, packed=r.packed)
+        return res, r.as_np, acts
 
     def policy_trace(self, batch, hidden0=None, which="both", want=("probs", "entropy", "greedy", "logp", "values", "stats"), return_hidden=False):
         """What would these actors and critics have done on a recorded episode batch, step by step?  ``batch``: what
@@ -267,19 +298,8 @@ class DcntrlMAC:
             raise NotImplementedError("saliency covers layer_N = recurrent_N = 1 only")
         want = tuple(want)
         assert all(k in ("entity", "input_grad", "act") for k in want), want
-        nA, N, M = self.n_agents, a.max_vehicle_num, a.rnn_hidden_dim
-        as_np = isinstance(batch["history"], np.ndarray)
-
-        def dev(t, dtype=None):
-            return self._dev(th.as_tensor(t) if isinstance(t, np.ndarray) else t, dtype)
-
-        def field(key, dtype=None):
-            """[E, T1, ...] on the device, rows addressable as e * T1 + t (a copy only when the batch's layout is not that)"""
-            t = dev(batch[key], dtype)
-            return t if t.stride(0) == t.shape[1] * t.stride(1) and t[0, 0].is_contiguous() else t.contiguous()
-
-        hist = field("history", th.float32)
-        E, T1 = hist.shape[:2]
+        nA, M = self.n_agents, a.rnn_hidden_dim
+        T1 = batch["history"].shape[1]
         one = isinstance(steps, (int, np.integer))
         if steps is None:
             t0, S = 0, T1
@@ -289,44 +309,20 @@ class DcntrlMAC:
             t0, t1, stride = steps.indices(T1)
             assert stride == 1, "steps: a slice with step 1"
             S = t1 - t0
-        assert 0 <= t0 and S >= 1 and t0 + S <= T1, (steps, T1)
-        sl = slice(t0, t0 + S)
-        sources = []
-        for key, w in self._widths():
-            view = (hist if key == "history" else field(key, th.float32))[:, sl]                  # [E, S, nA, N, w]
-            sources.append((view, w, view.stride(2), view.stride(1)))
-        acts = field("actions")[..., 0]                                                           # [E, T1, nA] int64
-        last, la_strides = None, (0, 0)
-        if a.obs_last_action:
-            last = th.cat([th.full_like(acts[:, :1], -1), acts[:, :-1]], 1)[:, sl]                # the action of t - 1; none at t = 0
-            la_strides = (last.stride(2), last.stride(1))
-        spec = ops.AcFeatureSpec(N, sources, n_actions=a.n_actions if a.obs_last_action else 0, last_action=last, la_strides=la_strides,
-                                 n_id=nA if a.obs_agent_id else 0, T=S, T_phys=T1)
-        assert spec.F == self.input_shape, (spec.F, self.input_shape)
-        avail = field("avail_actions")
-        if avail.dtype != th.int32:
-            avail = avail.to(th.int32)
-        avail = avail[:, sl]
+        r = self._rows(batch, t0, S)
+        E, as_np = r.E, r.as_np
         if hidden is None:
-            ha, hc = field("rnn_states_actors", th.float32)[:, sl], field("rnn_states_critics", th.float32)[:, sl]
+            ha, hc = r.field("rnn_states_actors", th.float32)[:, r.sl], r.field("rnn_states_critics", th.float32)[:, r.sl]
         else:
-            ha, hc = (dev(h, th.float32) for h in hidden)
+            ha, hc = (r.dev(h, th.float32) for h in hidden)
         assert ha.shape == hc.shape == (E, S, nA, M), (ha.shape, hc.shape, (E, S, nA, M))
         if ha.stride() != hc.stride() or ha.stride(3) != 1:
             ha, hc = ha.contiguous(), hc.contiguous()
-        tgt, tgt_all = None, -1
-        if isinstance(target, str):
-            assert target in ("recorded", "greedy"), target
-            if target == "recorded":
-                tgt = acts[:, sl]
-        else:
-            tgt = dev(target, th.int64)
-            assert tgt.shape == (E, S, nA), (tgt.shape, (E, S, nA))
+        tgt, tgt_strides = self._target(r, target)
         w = {"actor": 0, "critic": 1, "both": 2}[which]
-        esn = lambda t: (t.stride(2), t.stride(0), t.stride(1))                                   # noqa: E731  (net, chain, step)
-        res = ops.saliency(self.actor_arena, self.critic_arena, w, spec, E, S, nA, h_actor=ha, h_critic=hc, h_strides=esn(ha),
-                           avail=avail, avail_strides=esn(avail), target=tgt, target_strides=esn(tgt) if tgt is not None else (0, 0, 0),
-                           target_all=tgt_all, n_actions=a.n_actions, want=("y",) + want, packed=self.fc1_pack.get(spec))
+        res = ops.saliency(self.actor_arena, self.critic_arena, w, r.spec, E, S, nA, h_actor=ha, h_critic=hc, h_strides=_esn(ha),
+                           avail=r.avail, avail_strides=_esn(r.avail), target=tgt, target_strides=tgt_strides, target_all=-1,
+                           n_actions=a.n_actions, want=("y",) + want, packed=r.packed)
         out = {"sources": tuple(k for k, _ in self._widths())}
         for k in ("logp", "values", "target_action"):
             if k in res:
@@ -374,8 +370,7 @@ class DcntrlMAC:
             raise NotImplementedError("saliency_trace covers layer_N = recurrent_N = 1 only")
         want = tuple(want)
         assert all(k in ("entity", "input_grad", "act", "carry") for k in want), want
-        nA, N, M = self.n_agents, a.max_vehicle_num, a.rnn_hidden_dim
-        as_np = isinstance(batch["history"], np.ndarray)
+        nA, M = self.n_agents, a.rnn_hidden_dim
         T1 = batch["history"].shape[1]
         if steps is None:
             t0, S = 0, T1
@@ -389,20 +384,11 @@ class DcntrlMAC:
         if isinstance(lags, bool) or not isinstance(lags, (int, np.integer)) or not 0 <= lags < S:
             raise ValueError(f"saliency_trace: lags={lags!r} is not an int in [0, {S - 1}]")
         K1 = int(lags) + 1
-        sl = slice(t0, t0 + S)
-
-        def dev(t, dtype=None):
-            return self._dev(th.as_tensor(t) if isinstance(t, np.ndarray) else t, dtype)
-
-        def field(key, dtype=None):
-            """[E, T1, ...] on the device, rows addressable as e * T1 + t (a copy only when the batch's layout is not that)"""
-            t = dev(batch[key], dtype)
-            return t if t.stride(0) == t.shape[1] * t.stride(1) and t[0, 0].is_contiguous() else t.contiguous()
-
+        r = self._rows(batch, t0, S)                                                              # the rows, as saliency() describes them
+        E, as_np, dev = r.E, r.as_np, r.dev
         # 1: the chain from hidden0, and the state entering every step: cat(hidden0, h[:, :-1])
         w = {"actor": 0, "critic": 1, "both": 2}[which]
-        tr, _, _ = self._trace(batch, t0, S, hidden0, which, (), True)
-        E = tr["h_last_actor" if w != 1 else "h_last_critic"].shape[1]
+        tr, _, _ = self._trace(batch, t0, S, hidden0, which, (), True, rows=r)
         enter = {}
         for k, (net, on) in enumerate((("actor", w != 1), ("critic", w != 0))):
             if not on:
@@ -410,50 +396,23 @@ class DcntrlMAC:
             if isinstance(hidden0, str):
                 h0 = th.zeros(nA, E, 1, M, dtype=th.float32, device=self.device)
             elif hidden0 is None:
-                h0 = field("rnn_states_" + net + "s", th.float32)[:, t0].permute(1, 0, 2).unsqueeze(2)
+                h0 = r.field("rnn_states_" + net + "s", th.float32)[:, t0].permute(1, 0, 2).unsqueeze(2)
             else:
                 h0 = dev(hidden0[k], th.float32).permute(1, 0, 2).unsqueeze(2)
             enter[net] = th.cat([h0, tr["h_" + net][:, :, :-1]], 2)                                # [nA, E, S, M], contiguous
-        # 2: the rows, as saliency() describes them
-        hist = field("history", th.float32)
-        sources = []
-        for key, wd in self._widths():
-            view = (hist if key == "history" else field(key, th.float32))[:, sl]                  # [E, S, nA, N, w]
-            sources.append((view, wd, view.stride(2), view.stride(1)))
-        acts = field("actions")[..., 0]                                                           # [E, T1, nA] int64
-        last, la_strides = None, (0, 0)
-        if a.obs_last_action:
-            last = th.cat([th.full_like(acts[:, :1], -1), acts[:, :-1]], 1)[:, sl]                # the action of t - 1; none at t = 0
-            la_strides = (last.stride(2), last.stride(1))
-        spec = ops.AcFeatureSpec(N, sources, n_actions=a.n_actions if a.obs_last_action else 0, last_action=last, la_strides=la_strides,
-                                 n_id=nA if a.obs_agent_id else 0, T=S, T_phys=T1)
-        assert spec.F == self.input_shape, (spec.F, self.input_shape)
-        avail = field("avail_actions")
-        if avail.dtype != th.int32:
-            avail = avail.to(th.int32)
-        avail = avail[:, sl]
-        tgt = None
-        if isinstance(target, str):
-            assert target in ("recorded", "greedy"), target
-            if target == "recorded":
-                tgt = acts[:, sl]
-        else:
-            tgt = dev(target, th.int64)
-            assert tgt.shape == (E, S, nA), (tgt.shape, (E, S, nA))
-        esn = lambda t: (t.stride(2), t.stride(0), t.stride(1))                                   # noqa: E731  (net, chain, step)
+        tgt, tgt_strides = self._target(r, target)
         any_h = enter["actor" if w != 1 else "critic"]
-        # 3: lags + 1 launches
-        res = ops.saliency_lag(self.actor_arena, self.critic_arena, w, spec, E, S, nA, K1 - 1, h_actor=enter.get("actor"),
-                               h_critic=enter.get("critic"), h_strides=(any_h.stride(0), any_h.stride(1), any_h.stride(2)), avail=avail,
-                               avail_strides=esn(avail), target=tgt, target_strides=esn(tgt) if tgt is not None else (0, 0, 0),
-                               target_all=-1, n_actions=a.n_actions, want=("y", "entity") + tuple(k for k in want if k in ("input_grad", "act")),
-                               packed=self.fc1_pack.get(spec))
+        # 2: lags + 1 launches
+        res = ops.saliency_lag(self.actor_arena, self.critic_arena, w, r.spec, E, S, nA, K1 - 1, h_actor=enter.get("actor"),
+                               h_critic=enter.get("critic"), h_strides=(any_h.stride(0), any_h.stride(1), any_h.stride(2)), avail=r.avail,
+                               avail_strides=_esn(r.avail), target=tgt, target_strides=tgt_strides, target_all=-1, n_actions=a.n_actions,
+                               want=("y", "entity") + tuple(k for k in want if k in ("input_grad", "act")), packed=r.packed)
         lag_valid = th.arange(S, device=self.device)[:, None] >= th.arange(K1, device=self.device)[None, :]        # [S, K+1]
         out = {"sources": tuple(k for k, _ in self._widths()), "lag_valid": lag_valid}
         for k in ("logp", "values", "target_action"):
             if k in res:
                 out[k] = res[k].permute(1, 2, 0)
-        filled = dev(batch["filled"]).reshape(-1, T1)[:, sl].to(th.float64)                      # [E, S]
+        filled = dev(batch["filled"]).reshape(-1, T1)[:, r.sl].to(th.float64)                    # [E, S]
         for net in enter:
             out["h_" + net] = tr["h_" + net].permute(1, 2, 0, 3)
             ent = res["entity_" + net]                                                            # [nA, E, S, K+1, N, n_src, 2]

@@ -91,6 +91,35 @@ class Prediction_policy:
         return out.cpu().numpy() if as_np else out
 
     # ---------------------------------------------------------------------------- inference
+    def _beh_latent(self, who, behavior_latent, shape=None):
+        """the behaviour latent the GAT of ``who``'s call reads, fp32 on the device in the caller's layout (of ``shape``, where one is
+        given); None where this policy's GAT reads none"""
+        if not self.args.GAT_use_behavior:
+            return None
+        if behavior_latent is None:
+            raise ValueError(f"{who}: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
+        lat = _as_dev(behavior_latent, self.device)
+        if shape is not None and lat.shape != shape:
+            raise ValueError(f"{who}: behavior_latent {tuple(lat.shape)} != {shape}")
+        return lat
+
+    def _noise(self, noise, deterministic, nA, b0, b1, inner, zeros=True):
+        """the gumbel samples [nA, b1 - b0, *inner] of rows b0 .. b1 - 1: that slice of a given ``noise``, else a draw from torch's
+        generator; ``deterministic``: no noise -- zeros (l + 0 is exact: the gate of no noise), or None where the kernel takes that"""
+        if deterministic:
+            return torch.zeros(nA, b1 - b0, *inner, dtype=torch.float32, device=self.device) if zeros else None
+        if noise is not None:
+            return noise[:, b0:b1].to(device=self.device, dtype=torch.float32).contiguous()
+        return gumbel_noise((nA, b1 - b0, *inner), self.device)
+
+    def _start_offsets(self, hist):
+        """int64 [nA, E] on the device: the element offset of (env, agent, entity 0, feature 0) from the first element of ``hist``
+        [E, nA, N, d]; every row these offsets lead a kernel to lies inside hist's storage (checked here, on the host)"""
+        E, nA, N, d = hist.shape
+        offset = (torch.arange(nA)[:, None] * hist.stride(1) + torch.arange(E)[None, :] * hist.stride(0)).to(torch.int64)
+        assert int(offset.max()) + (N - 1) * hist.stride(2) + d <= ops._room(hist)
+        return offset.to(self.device)
+
     def predict(self, history_single, attention_hidden, behavior_latent=None, noise=None):
         """Where will the entities be in the next ``pred_length`` steps?  history_single [E,nA,N,d], attention_hidden
         [E,nA,N,A], behavior_latent [E,nA,N,Z] -> predicted states [E,nA,N,P,d]: one GAT forward and one decoder launch for
@@ -109,9 +138,7 @@ class Prediction_policy:
         if noise is None:
             noise = gumbel_noise((nA, E, N, N - 1, 2), self.device)
         h0, _ = ops.gat_forward(self.gat_arena, hist.permute(1, 0, 2, 3), lat, hid.permute(1, 0, 2, 3), noise)
-        offset = (torch.arange(nA)[:, None] * hist.stride(1) + torch.arange(E)[None, :] * hist.stride(0)).to(torch.int64)
-        assert int(offset.max()) + (N - 1) * hist.stride(2) + d <= hist.untyped_storage().nbytes() // 4 - hist.storage_offset()
-        out = ops.predict(self.dec_arena, hist, offset.to(self.device), hist.stride(2), 0, h0.reshape(nA, E * N, -1), N,
+        out = ops.predict(self.dec_arena, hist, self._start_offsets(hist), hist.stride(2), 0, h0.reshape(nA, E * N, -1), N,
                           self.pred_length, d, checked=True)
         pred = out["pred"].view(nA, E, N, self.pred_length, d).permute(1, 0, 2, 3, 4)
         return pred.cpu().numpy() if as_np else pred
@@ -157,8 +184,7 @@ class Prediction_policy:
         # the bound on what the kernel will read is checked here, without a read-back
         sE, sT, sA, sN, _ = history.stride()
         offset = (torch.arange(nA)[:, None] * sA + (ei * sE + ti * sT)[None, :]).to(torch.int64)
-        room = history.untyped_storage().nbytes() // 4 - history.storage_offset()
-        assert int(offset.max()) + (N - 1) * sN + P * sT + d <= room
+        assert int(offset.max()) + (N - 1) * sN + P * sT + d <= ops._room(history)
         offset = offset.to(dev)
         ei, ti = ei.to(dev), ti.to(dev)
         weight = ok.unfold(1, P + 1, 1).all(-1)[ei, ti].to(torch.float32).t().contiguous()      # [nA, S_all]
@@ -203,9 +229,8 @@ class Prediction_policy:
         as_np = isinstance(history_single, np.ndarray)
         hist = _as_dev(history_single, self.device).unsqueeze(1)
         hid = _as_dev(attention_hidden, self.device)
-        if self.args.GAT_use_behavior and behavior_latent is None:
-            raise ValueError("attention_map: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
-        lat = _as_dev(behavior_latent, self.device).unsqueeze(1) if self.args.GAT_use_behavior else None
+        lat = self._beh_latent("attention_map", behavior_latent)
+        lat = None if lat is None else lat.unsqueeze(1)
         if noise is not None and not deterministic:
             noise = _as_dev(noise, self.device).unsqueeze(2)
         res = self.attention_trace(hist, lat, hidden0=hid, noise=noise, deterministic=deterministic, want=("attention", "soft", "hard"),
@@ -248,11 +273,8 @@ class Prediction_policy:
         assert all(k in names for k in want), want
         if hist.stride(4) != 1 or hist.stride(3) != d:
             hist = hist.contiguous()
-        lat = None
-        if self.args.GAT_use_behavior:
-            if behavior_latent is None:
-                raise ValueError("attention_trace: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
-            lat = _as_dev(behavior_latent, dev)
+        lat = self._beh_latent("attention_trace", behavior_latent)
+        if lat is not None:
             if lat.stride(4) != 1 or lat.stride(3) != lat.shape[4]:
                 lat = lat.contiguous()
             lat = lat.permute(2, 0, 1, 3, 4)
@@ -279,12 +301,7 @@ class Prediction_policy:
         parts = []
         for e0 in range(0, E, max_envs_per_launch):
             e1 = min(E, e0 + max_envs_per_launch)
-            if deterministic:
-                nz = None
-            elif noise is not None:
-                nz = noise[:, e0:e1].to(device=dev, dtype=torch.float32).contiguous()
-            else:
-                nz = gumbel_noise((nA, e1 - e0, S, N, N - 1, 2), dev)
+            nz = self._noise(noise, deterministic, nA, e0, e1, (S, N, N - 1, 2), zeros=False)
             out = {"latent": res["latent"][e0:e1].permute(2, 0, 1, 3, 4)}
             for k in want:
                 out[names[k]] = res[k][e0:e1].permute(2, 0, 1, 3, 4)
@@ -325,6 +342,24 @@ class Prediction_policy:
         if chunk < 1:
             raise ValueError(f"{who}: max_workspace_mb={max_workspace_mb} is too small for one row ({per_row / (1 << 20):.1f} MB)")
         return chunk
+
+    def _gat_saliency_chunks(self, chunk, src0, lat, hid, noise, deterministic, tau, v, through, out, before=None, after=None):
+        """``chunk`` rows [nA, b0:b1] at a time: the training form of the GAT forward on src0 / lat / hid with the chunk's noise (the
+        record the backward reads), then ``ops.gat_saliency`` with the rows of ``v`` into the rows of the tensors in ``out`` (a dict
+        by output name).  ``before(b0, b1, noise)`` runs ahead of the two launches (``v`` may be what it writes), ``after(b0, b1,
+        record)`` behind them"""
+        nA, B, N, _ = src0.shape
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            nz = self._noise(noise, deterministic, nA, b0, b1, (N, N - 1, 2))
+            if before is not None:
+                before(b0, b1, nz)
+            _, saved = ops.gat_forward(self.gat_arena, src0[:, b0:b1], None if lat is None else lat[:, b0:b1], hid[:, b0:b1], nz, tau=tau,
+                                       save=True)
+            ops.gat_saliency(self.gat_arena, saved, v[:, b0:b1], gate_through=through, want=tuple(out),
+                             out={k: t[:, b0:b1] for k, t in out.items()})
+            if after is not None:
+                after(b0, b1, saved)
 
     def attention_saliency(self, history, behavior_latent=None, hidden=None, target="self", noise=None, deterministic=True,
                            gate="through", tau=None, want=("pair",), max_workspace_mb=256):
@@ -372,15 +407,9 @@ class Prediction_policy:
         if not tau > 0:
             raise ValueError(f"attention_saliency: tau={tau} must be positive")
         B = E * S
-        Z = 0
-        lat = None
-        if self.args.GAT_use_behavior:
-            if behavior_latent is None:
-                raise ValueError("attention_saliency: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
-            lat = _as_dev(behavior_latent, dev)
-            Z = self.args.latent_dim
-            if lat.shape != (E, S, nA, N, Z):
-                raise ValueError(f"attention_saliency: behavior_latent {tuple(lat.shape)} != {(E, S, nA, N, Z)}")
+        Z = self.args.latent_dim if self.args.GAT_use_behavior else 0
+        lat = self._beh_latent("attention_saliency", behavior_latent, (E, S, nA, N, Z))
+        if lat is not None:
             lat = lat.permute(2, 0, 1, 3, 4).reshape(nA, B, N, Z).contiguous()
         D = d + Z
         n_src = 2 if Z else 1
@@ -426,25 +455,17 @@ class Prediction_policy:
         res["target_vector"] = vt if vt is not None else res["latent"]
         act_h = torch.empty(nA, B, N, A, dtype=torch.bool, device=dev)
         act_v = torch.empty(nA, B, N, A, dtype=torch.bool, device=dev)
-        outs = tuple(k for k in ops.GAT_SALIENCY_OUTPUTS if k in res)
-        for b0 in range(0, B, chunk):
-            b1 = min(B, b0 + chunk)
-            if deterministic:
-                nz = torch.zeros(nA, b1 - b0, N, N - 1, 2, **f32)                  # l + 0 is exact: the gate of no noise
-            elif noise is not None:
-                nz = noise[:, b0:b1].contiguous()
-            else:
-                nz = gumbel_noise((nA, b1 - b0, N, N - 1, 2), dev)
-            s0, s1, h0 = src0[:, b0:b1], None if lat is None else lat[:, b0:b1], hid[:, b0:b1]
+
+        def rollout_latent(b0, b1, nz):
             # the rollout's bits of the latent: the inference form of the forward (attention_map's launch)
-            ops.gat_trace(self.gat_arena, s0.unsqueeze(2), None if s1 is None else s1.unsqueeze(2), h0, None if deterministic else nz.unsqueeze(2),
-                          tau=tau, want=("latent",), out={"latent": res["latent"][:, b0:b1].unsqueeze(2)})
-            # the record the backward reads: the training form of the same forward
-            _, saved = ops.gat_forward(self.gat_arena, s0, s1, h0, nz, tau=tau, save=True)
-            ops.gat_saliency(self.gat_arena, saved, res["target_vector"][:, b0:b1], gate_through=through, want=outs,
-                             out={k: res[k][:, b0:b1] for k in outs})
+            ops.gat_trace(self.gat_arena, src0[:, b0:b1].unsqueeze(2), None if lat is None else lat[:, b0:b1].unsqueeze(2), hid[:, b0:b1],
+                          None if deterministic else nz.unsqueeze(2), tau=tau, want=("latent",), out={"latent": res["latent"][:, b0:b1].unsqueeze(2)})
+
+        def active(b0, b1, saved):
             act_h[:, b0:b1] = saved["h_enc"].view(nA, b1 - b0, N, A) > 0
             act_v[:, b0:b1] = saved["qkv"].view(nA, b1 - b0, N, 3 * A)[..., 2 * A:] > 0
+        self._gat_saliency_chunks(chunk, src0, lat, hid, noise, deterministic, tau, res["target_vector"], through,
+                                  {k: res[k] for k in ops.GAT_SALIENCY_OUTPUTS if k in res}, before=rollout_latent, after=active)
         res["active_h"], res["active_v"] = act_h, act_v
         res = {k: v.unflatten(1, (E, S)).permute(1, 2, 0, *range(3, v.dim() + 1)) for k, v in res.items()}
         return {k: v.cpu().numpy() for k, v in res.items()} if as_np else res
@@ -509,14 +530,9 @@ class Prediction_policy:
             raise ValueError(f"{who}: noise was given together with deterministic=True")
         if not isinstance(presence_col, (int, np.integer)) or presence_col >= d:
             raise ValueError(f"{who}: presence_col={presence_col!r} outside the {d} columns")
-        Z, lat = 0, None
-        if self.args.GAT_use_behavior:
-            if behavior_latent is None:
-                raise ValueError(f"{who}: this policy's GAT reads the behaviour latent (GAT_use_behavior), behavior_latent is needed")
-            lat = _as_dev(behavior_latent, dev)
-            Z = self.args.latent_dim
-            if lat.shape != (E, nA, N, Z):
-                raise ValueError(f"{who}: behavior_latent {tuple(lat.shape)} != {(E, nA, N, Z)}")
+        Z = self.args.latent_dim if self.args.GAT_use_behavior else 0
+        lat = self._beh_latent(who, behavior_latent, (E, nA, N, Z))
+        if lat is not None:
             lat = lat.permute(1, 0, 2, 3).contiguous()
         if noise is not None:
             noise = _as_dev(noise, dev)
@@ -570,20 +586,13 @@ class Prediction_policy:
         if hist.stride(3) != 1:
             hist = hist.contiguous()
         src0, hprev = hist.permute(1, 0, 2, 3), hid.permute(1, 0, 2, 3)
-        if deterministic:
-            nz = torch.zeros(nA, E, N, N - 1, 2, **f32)                            # l + 0 is exact: the gate of no noise
-        elif noise is not None:
-            nz = noise
-        else:
-            nz = gumbel_noise((nA, E, N, N - 1, 2), dev)
+        nz = self._noise(noise, deterministic, nA, 0, E, (N, N - 1, 2))
         h0, _ = ops.gat_forward(self.gat_arena, src0, lat, hprev, nz)              # predict()'s launch: the rollout's bits
-        offset = (torch.arange(nA)[:, None] * hist.stride(1) + torch.arange(E)[None, :] * hist.stride(0)).to(torch.int64)
-        assert int(offset.max()) + (N - 1) * hist.stride(2) + d <= hist.untyped_storage().nbytes() // 4 - hist.storage_offset()
         grads = "grad" in want or ks is not None
         names = ("state_l1", "latent_l1", "pred") + (("state_gxi", "latent_gxi") if "summary" in want else ()) \
             + (("state_grad", "latent_grad") if grads else ()) + (("active",) if "act" in want else ())
-        got = ops.pdec_saliency(self.dec_arena, hist, offset.to(dev), hist.stride(2), h0.reshape(nA, E * N, A), N, P, d, jobs, v=vt, want=names,
-                                checked=True)
+        got = ops.pdec_saliency(self.dec_arena, hist, self._start_offsets(hist), hist.stride(2), h0.reshape(nA, E * N, A), N, P, d, jobs, v=vt,
+                                want=names, checked=True)
 
         def rows(t, *inner):                                                       # [nA, E*N, ...] -> [E, nA, N, ...]
             return t.view(nA, E, N, *inner).permute(1, 0, 2, *range(3, 3 + len(inner)))
@@ -602,14 +611,8 @@ class Prediction_policy:
             pair_gl1, pair_gxi = torch.empty(nA, E, N, N, n_src, **f32), torch.empty(nA, E, N, N, n_src, **f32)
             ig = torch.empty(nA, E, N, D, **f32)
             v_gat = got["latent_grad"][:, :, ks].contiguous().view(nA, E, N, A)
-            outs = ("pair_gl1", "pair_gxi", "input_grad")
-            for b0 in range(0, E, chunk):
-                b1 = min(E, b0 + chunk)
-                # the record the backward reads: the training form of the same forward
-                _, saved = ops.gat_forward(self.gat_arena, src0[:, b0:b1], None if lat is None else lat[:, b0:b1], hprev[:, b0:b1],
-                                           nz[:, b0:b1].contiguous(), save=True)
-                ops.gat_saliency(self.gat_arena, saved, v_gat[:, b0:b1], gate_through=through, want=outs,
-                                 out={"pair_gl1": pair_gl1[:, b0:b1], "pair_gxi": pair_gxi[:, b0:b1], "input_grad": ig[:, b0:b1]})
+            self._gat_saliency_chunks(chunk, src0, lat, hprev, nz, False, 0.01, v_gat, through,
+                                      dict(pair_gl1=pair_gl1, pair_gxi=pair_gxi, input_grad=ig))
             ig[..., :d] += got["state_grad"][:, :, ks].view(nA, E, N, d)           # the direct path: each entity's own start state
             res.update(pair_gl1=pair_gl1.permute(1, 0, 2, 3, 4), pair_gxi=pair_gxi.permute(1, 0, 2, 3, 4), input_grad=ig.permute(1, 0, 2, 3))
         # own state against social context, per horizon: ONE host read-back

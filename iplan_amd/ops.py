@@ -116,6 +116,11 @@ def gat_forward(arena, src0, src1, h_prev, noise, tau=0.01, save=False, out=None
     return out, saved
 
 
+def _room(t):
+    """elements from t's first element to the end of its storage"""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
 def _nbs_strides(t, inner, what):
     """t is logically [n_nets, B, S, <inner dims contiguous>] with non-negative strides; returns (s_net, s_b, s_step) in elements
     after checking on the host that the last element the kernel can touch lies inside t's storage."""
@@ -127,9 +132,23 @@ def _nbs_strides(t, inner, what):
     assert expect == inner, (what, expect, inner)
     s = t.stride()[:3]
     assert all(x >= 0 for x in s), (what, s)
-    room = t.untyped_storage().nbytes() // 4 - t.storage_offset()
-    assert sum((t.shape[d] - 1) * s[d] for d in range(3)) + inner <= room, (what, "reaches outside its storage", t.shape, s, room)
+    reach = sum((t.shape[d] - 1) * s[d] for d in range(3)) + inner
+    assert reach <= _room(t), (what, "reaches outside its storage", t.shape, s, _room(t))
     return s
+
+
+def _dest_nbs(out, res, k, lead, inner, dev):
+    """``out[k]`` if the caller gave one, else a fresh tensor: float32 [*lead, *inner] whose dims before ``inner`` may be strided (lead =
+    (n_nets, B) or (n_nets, B, S)); entered into ``res``, checked to lie inside its storage -> (tensor, s_net, s_b, s_step)"""
+    t = None if out is None else out.get(k)
+    if t is None:
+        t = torch.empty(*lead, *inner, dtype=torch.float32, device=dev)
+    assert t.shape == tuple(lead) + tuple(inner) and t.device == dev, (k, t.shape)
+    n_in = 1
+    for x in inner:
+        n_in *= x
+    res[k] = t
+    return (t,) + tuple(_nbs_strides(t if len(lead) == 3 else t.unsqueeze(2), n_in, k))
 
 
 GAT_TRACE_OUTPUTS = ("latent", "soft", "hard", "attn", "stats")
@@ -190,12 +209,7 @@ def gat_trace_args(arena, src0, src1=None, hidden0=None, noise=None, tau=0.01, w
     res = {}
     for k in want:
         inner = {"latent": (N, A), "stats": (L.GAT_TRACE_NSTAT,)}.get(k, (N, N))
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(n_nets, B, S, *inner, dtype=torch.float32, device=dev)
-        assert t.shape == (n_nets, B, S) + inner and t.device == dev, (k, t.shape)
-        n_in = inner[0] * (inner[1] if len(inner) > 1 else 1)
-        s = _nbs_strides(t, n_in, k)
+        t, *s = _dest_nbs(out, res, k, (n_nets, B, S), inner, dev)
         setattr(a, k, t.data_ptr())
         if k == "stats":
             assert t.is_contiguous()
@@ -203,7 +217,6 @@ def gat_trace_args(arena, src0, src1=None, hidden0=None, noise=None, tau=0.01, w
             pre = "lat" if k == "latent" else k
             for name, v in zip(("net", "b", "step"), s):
                 setattr(a, f"{pre}_s_{name}", v)
-        res[k] = t
     return a, res
 
 
@@ -258,14 +271,7 @@ def gat_saliency_args(arena, saved, v, gate_through=True, want=("input_grad",), 
     pre = {"grad": "grad", "input_grad": "ig", "hidden_grad": "hg"}
     pair = None
     for k in want:
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(n_nets, B, *inner[k], dtype=torch.float32, device=dev)
-        assert t.shape == (n_nets, B) + inner[k] and t.device == dev, (k, t.shape)
-        n_in = 1
-        for x in inner[k]:
-            n_in *= x
-        s_net, s_b, _ = _nbs_strides(t.unsqueeze(2), n_in, k)
+        t, s_net, s_b, _ = _dest_nbs(out, res, k, (n_nets, B), inner[k], dev)
         setattr(a, k, t.data_ptr())
         if k in pre:
             setattr(a, pre[k] + "_s_net", s_net)
@@ -274,7 +280,6 @@ def gat_saliency_args(arena, saved, v, gate_through=True, want=("input_grad",), 
             assert pair is None or pair == (s_net, s_b), "pair_gl1 and pair_gxi share their strides"
             pair = (s_net, s_b)
             a.pair_s_net, a.pair_s_b = s_net, s_b
-        res[k] = t
     return a, res, keep
 
 
@@ -529,8 +534,52 @@ POLICY_TRACE_OUTPUTS = ("probs", "entropy", "greedy", "logp", "values", "h_actor
 
 def _inside(t, reach, what):
     """the last element a kernel can touch through ``t.data_ptr()``, ``reach`` elements past it, lies inside t's storage"""
-    room = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
-    assert 0 <= reach <= room, (what, "reaches outside its storage", reach, room)
+    assert 0 <= reach <= _room(t), (what, "reaches outside its storage", reach, _room(t))
+
+
+def _dest(out, res, k, shape, dtype, dev, fresh=torch.empty):
+    """``out[k]`` if the caller gave one, else a ``fresh`` tensor: contiguous, of exactly ``shape`` and ``dtype`` on ``dev``; entered
+    into ``res`` -> its address"""
+    t = None if out is None else out.get(k)
+    if t is None:
+        t = fresh(*shape, dtype=dtype, device=dev)
+    assert t.shape == tuple(shape) and t.dtype == dtype and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
+    res[k] = t
+    return t.data_ptr()
+
+
+def _ac_rows(a, actor_arena, critic_arena, which, spec, E, S, n_agents):
+    """What every launch over E x S recorded rows of the actors / critics checks and enters into its descriptor ``a``: ``which``, the
+    sizes, one trunk activation for both arenas, ``spec`` (T = S) with every feature source and the last action inside their storage
+    -> (the device, the largest physical row)"""
+    assert which in (0, 1, 2) and E >= 1 and S >= 1 and n_agents >= 1, (which, E, S, n_agents)
+    arena0 = actor_arena if which != 1 else critic_arena
+    dev = arena0.data.device
+    a.n_agents, a.E, a.S, a.which = n_agents, E, S, which
+    a.act_tanh = int(bool(getattr(arena0, "act_tanh", False)))
+    if which == 2:
+        assert bool(getattr(actor_arena, "act_tanh", False)) == bool(getattr(critic_arena, "act_tanh", False)), \
+            "actor and critic of one launch must use the same trunk activation (args.use_ReLU)"
+    assert spec.T == S and spec.T_phys >= S, (spec.T, spec.T_phys, S)
+    spec.fill(a.feat)
+    last_row = (E - 1) * spec.T_phys + S - 1                         # the largest physical row
+    for t, w, s_net, s_row in spec.sources:
+        assert t.device == dev and min(s_net, s_row) >= 0
+        _inside(t, (n_agents - 1) * s_net + last_row * s_row + spec.N * w, "feature source")
+    if spec.last_action is not None and spec.n_actions > 0:
+        assert spec.last_action.device == dev and min(spec.la_strides) >= 0
+        _inside(spec.last_action, (n_agents - 1) * spec.la_strides[0] + last_row * spec.la_strides[1] + 1, "last_action")
+    return dev, last_row
+
+
+def _ac_packed(a, which, packed):
+    """``packed``: Fc1Pack.get(spec) or None; the fragment part (and gamma) is all these kernels read"""
+    if packed is not None:
+        pa, pc = packed
+        if which != 1:
+            a.packed_actor, a.packed_s_net = pa.data_ptr(), pa.stride(0)
+        if which != 0:
+            a.packed_critic, a.packed_s_net = pc.data_ptr(), pc.stride(0)
 
 
 def policy_trace(actor_arena, critic_arena, which, spec, E, S, n_agents, hidden0_actor=None, hidden0_critic=None, h_strides=(0, 0),
@@ -560,37 +609,15 @@ def policy_trace_args(actor_arena, critic_arena, which, spec, E, S, n_agents, hi
                       want=("probs", "entropy", "greedy", "logp", "values"), packed=None, out=None):
     """The descriptor of a ``policy_trace`` launch, its output tensors and the operands to keep alive until the launch has been
     queued, checked but not launched: (IplanAcTraceArgs, dict, tuple)."""
-    assert which in (0, 1, 2) and E >= 1 and S >= 1 and n_agents >= 1, (which, E, S, n_agents)
     want = tuple(want)
     assert all(k in POLICY_TRACE_OUTPUTS for k in want), want
-    arena0 = actor_arena if which != 1 else critic_arena
-    dev = arena0.data.device
     M = L.AC_HIDDEN
     a = L.AcTraceArgs()
-    a.n_agents, a.E, a.S, a.which = n_agents, E, S, which
-    a.act_tanh = int(bool(getattr(arena0, "act_tanh", False)))
-    if which == 2:
-        assert bool(getattr(actor_arena, "act_tanh", False)) == bool(getattr(critic_arena, "act_tanh", False)), \
-            "actor and critic of one trace must use the same trunk activation (args.use_ReLU)"
-    assert spec.T == S and spec.T_phys >= S, (spec.T, spec.T_phys, S)
-    spec.fill(a.feat)
-    last_row = (E - 1) * spec.T_phys + S - 1                         # the largest physical row
-    for t, w, s_net, s_row in spec.sources:
-        assert t.device == dev and min(s_net, s_row) >= 0
-        _inside(t, (n_agents - 1) * s_net + last_row * s_row + spec.N * w, "feature source")
-    if spec.last_action is not None and spec.n_actions > 0:
-        assert spec.last_action.device == dev and min(spec.la_strides) >= 0
-        _inside(spec.last_action, (n_agents - 1) * spec.la_strides[0] + last_row * spec.la_strides[1] + 1, "last_action")
-    f32 = dict(dtype=torch.float32, device=dev)
+    dev, last_row = _ac_rows(a, actor_arena, critic_arena, which, spec, E, S, n_agents)
     res = {}
 
     def dest(k, shape, dtype=torch.float32):
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(*shape, dtype=dtype, device=dev)
-        assert t.shape == tuple(shape) and t.dtype == dtype and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
-        res[k] = t
-        return t.data_ptr()
+        return _dest(out, res, k, shape, dtype, dev)
 
     for net, h0, key in ((0, hidden0_actor, "actor"), (1, hidden0_critic, "critic")):
         if which == 1 - net:
@@ -627,12 +654,7 @@ def policy_trace_args(actor_arena, critic_arena, which, spec, E, S, n_agents, hi
         _fill_acnet(a.critic, critic_arena, L.CRITIC_PARAM_ORDER, 1)
         if "values" in want:
             a.values = dest("values", (n_agents, E, S))
-    if packed is not None:                                 # Fc1Pack.get(spec): the fragment part is all the trunk reads
-        pa, pc = packed
-        if which != 1:
-            a.packed_actor, a.packed_s_net = pa.data_ptr(), pa.stride(0)
-        if which != 0:
-            a.packed_critic, a.packed_s_net = pc.data_ptr(), pc.stride(0)
+    _ac_packed(a, which, packed)
     gi = workspace(dev, 2 * n_agents * E * S * L.AC_TRACE_GI, "ac_trace")
     a.gi = gi.data_ptr()
     return a, res, (spec, hidden0_actor, hidden0_critic, avail, actions_in, packed, gi)
@@ -668,37 +690,17 @@ def saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_acto
                   out=None):
     """The descriptor of a ``saliency`` launch, its output tensors and the operands to keep alive until the launch has been queued,
     checked but not launched: (IplanAcSaliencyArgs, dict, tuple)."""
-    assert which in (0, 1, 2) and E >= 1 and S >= 1 and n_agents >= 1, (which, E, S, n_agents)
     want = tuple(want)
     assert want and all(k in SALIENCY_OUTPUTS for k in want), want
-    arena0 = actor_arena if which != 1 else critic_arena
-    dev = arena0.data.device
     M = L.AC_HIDDEN
     a = L.AcSaliencyArgs()
-    a.n_agents, a.E, a.S, a.which, a.target_all = n_agents, E, S, which, target_all
-    a.act_tanh = int(bool(getattr(arena0, "act_tanh", False)))
-    if which == 2:
-        assert bool(getattr(actor_arena, "act_tanh", False)) == bool(getattr(critic_arena, "act_tanh", False)), \
-            "actor and critic of one launch must use the same trunk activation (args.use_ReLU)"
-    assert spec.T == S and spec.T_phys >= S, (spec.T, spec.T_phys, S)
-    spec.fill(a.feat)
-    last_row = (E - 1) * spec.T_phys + S - 1                         # the largest physical row
-    for t, w, s_net, s_row in spec.sources:
-        assert t.device == dev and min(s_net, s_row) >= 0
-        _inside(t, (n_agents - 1) * s_net + last_row * s_row + spec.N * w, "feature source")
-    if spec.last_action is not None and spec.n_actions > 0:
-        assert spec.last_action.device == dev and min(spec.la_strides) >= 0
-        _inside(spec.last_action, (n_agents - 1) * spec.la_strides[0] + last_row * spec.la_strides[1] + 1, "last_action")
+    dev, _ = _ac_rows(a, actor_arena, critic_arena, which, spec, E, S, n_agents)
+    a.target_all = target_all
     n_src = sum(1 for s in spec.sources if s[1] > 0)
     res = {}
 
     def dest(k, shape, dtype=torch.float32):
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(*shape, dtype=dtype, device=dev)
-        assert t.shape == tuple(shape) and t.dtype == dtype and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
-        res[k] = t
-        return t.data_ptr()
+        return _dest(out, res, k, shape, dtype, dev)
 
     def reach(strides, width):
         assert len(strides) == 3 and min(strides) >= 0, strides
@@ -737,12 +739,7 @@ def saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_acto
         _fill_acnet(a.critic, critic_arena, L.CRITIC_PARAM_ORDER, 1)
         if "y" in want:
             a.values = dest("values", (n_agents, E, S))
-    if packed is not None:                                 # Fc1Pack.get(spec): the fragment part and gamma are all the kernel reads
-        pa, pc = packed
-        if which != 1:
-            a.packed_actor, a.packed_s_net = pa.data_ptr(), pa.stride(0)
-        if which != 0:
-            a.packed_critic, a.packed_s_net = pc.data_ptr(), pc.stride(0)
+    _ac_packed(a, which, packed)
     return a, res, (spec, h_actor, h_critic, avail, target, packed)
 
 
@@ -787,11 +784,7 @@ def saliency_lag_args(actor_arena, critic_arena, which, spec, E, S, n_agents, la
             shapes["input_grad_" + key] = (n_agents, E, S, K1, spec.F)
     lagged = {}
     for k, shape in shapes.items():
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.zeros(*shape, dtype=torch.float32, device=dev)
-        assert t.shape == shape and t.dtype == torch.float32 and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
-        lagged[k] = t
+        _dest(out, lagged, k, shape, torch.float32, dev, fresh=torch.zeros)
     # the row description, the checks and the lag-0-only outputs are saliency's; the lagged outputs are set below
     base, res, keep = saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor, h_critic, h_strides, avail, avail_strides,
                                     target, target_strides, target_all, n_actions, tuple(k for k in want if k in ("y", "act")) or ("y",), packed,
@@ -856,12 +849,7 @@ def ppo_eval_args(logp, entropy, values, old_logp, adv, value_preds, returns, ma
     res = {}
 
     def dest(k, shape):
-        t = None if out is None else out.get(k)
-        if t is None:
-            t = torch.empty(*shape, dtype=torch.float32, device=dev)
-        assert t.shape == tuple(shape) and t.dtype == torch.float32 and t.device == dev and t.is_contiguous(), (k, t.shape, t.dtype)
-        res[k] = t
-        return t.data_ptr()
+        return _dest(out, res, k, shape, torch.float32, dev)
 
     a.stats = dest("stats", (nA, len(L.PPO_EVAL_STATS)))
     a.step_stats = dest("step_stats", (nA, max(T, 0), len(L.PPO_EVAL_STEP_STATS)))
@@ -1423,14 +1411,12 @@ def predict(arena, hist, offset, ent_stride, step_stride, h0, N, P, d, want_pred
     if not want_metrics:
         target = None
 
-    def room(t):                                            # elements from t's first element to the end of its storage
-        return t.untyped_storage().nbytes() // 4 - t.storage_offset()
     if not checked:
         lo, hi = int(offset.min()), int(offset.max())
-        assert lo >= 0 and hi + (N - 1) * ent_stride + d <= room(hist), ("start rows outside hist", lo, hi, room(hist))
+        assert lo >= 0 and hi + (N - 1) * ent_stride + d <= _room(hist), ("start rows outside hist", lo, hi, _room(hist))
         if target is not None:
             assert target.dtype == torch.float32 and target.device == dev
-            assert hi + (N - 1) * ent_stride + P * step_stride + d <= room(target), ("target rows outside target", hi, room(target))
+            assert hi + (N - 1) * ent_stride + P * step_stride + d <= _room(target), ("target rows outside target", hi, _room(target))
     a = L.PredictArgs()
     a.n_nets, a.S, a.N, a.P, a.d = n_nets, S, N, P, d
     a.x0, a.offset, a.ent_stride, a.step_stride, a.h0 = hist.data_ptr(), offset.data_ptr(), ent_stride, step_stride, h0.data_ptr()

@@ -459,9 +459,28 @@ def _codes():
     return vals["IPLAN_EINVAL"]
 
 
+def assert_out_refused(call, bufs, keys):
+    """``call(out)`` raises AssertionError when ``out[k]``, k in ``keys``, has the wrong shape, the wrong dtype or is not contiguous, the
+    other destinations being the good views of the sentinel-filled ``bufs`` (which the caller then finds untouched: nothing was launched)"""
+    good = {k: v[2] for k, v in bufs.items()}
+    for k in keys:
+        t = good[k]
+        assert t.numel() > 1
+        strided = torch.zeros(*t.shape, 2, dtype=t.dtype, device=t.device)[..., 0]
+        assert strided.shape == t.shape and not strided.is_contiguous()
+        for what, bad in (("shape", t.unsqueeze(0)), ("dtype", t.to(torch.float64)), ("not contiguous", strided)):
+            try:
+                call({**good, k: bad})
+            except AssertionError:
+                pass
+            else:
+                raise AssertionError(f"out[{k!r}] of the wrong {what} was not refused")
+
+
 def check_bad_arguments(device, dims=(2, 2, 3, 3, 5, 5)):
-    """9: each invalid descriptor is refused by the host-side check with IPLAN_EINVAL and a message; nothing is launched, so the
-    sentinel-filled outputs of the descriptor stay as they were"""
+    """9: each invalid descriptor is refused by the host-side check with IPLAN_EINVAL and a message; an ``out=`` destination of the wrong
+    shape or dtype, or a non-contiguous one, makes ops.policy_trace raise AssertionError; nothing is launched, so the sentinel-filled
+    outputs of the descriptor stay as they were"""
     case = get_case(dims, device)
     nA, E, S, N, d, n_act = dims
     good = case.run()
@@ -502,6 +521,9 @@ def check_bad_arguments(device, dims=(2, 2, 3, 3, 5, 5)):
     refused(ref, which=3)
     refused(ref, gi=None)
     refused(ref, actions_in=None)                             # logp is asked for
+    assert_out_refused(lambda out: ops.policy_trace(case.mac.actor_arena, case.mac.critic_arena, 2, spec, E, S, nA, avail=av,
+                                                    avail_strides=(av.stride(2), av.stride(1)), actions_in=ac, act_strides=(ac.stride(2), ac.stride(1)),
+                                                    n_actions=n_act, want=OUTS, out=out), bufs, ("probs", "greedy", "h_last_critic"))
     _sync(device)
     for k, (sent, buf, _) in bufs.items():
         assert torch.equal(buf.cpu(), sent), (k, "a refused call wrote an output")

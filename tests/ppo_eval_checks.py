@@ -18,6 +18,7 @@ from iplan_amd import _lib as L
 from iplan_amd import ops
 from oracle import iplan_oracle as O
 from tests.oracle_checks import E32_FACTOR, _fields, _Log
+from tests.policy_trace_checks import assert_out_refused
 
 TOL = 1e-5
 C = L.PPO_EVAL_CHUNK
@@ -395,8 +396,9 @@ def _einval():
 
 
 def check_bad_arguments(device, shape=(3, 5, 9, 36)):
-    """9: each invalid descriptor is refused by the host-side check with IPLAN_EINVAL and a message; nothing is launched, so the
-    sentinel-filled outputs stay as they were"""
+    """9: each invalid descriptor is refused by the host-side check with IPLAN_EINVAL and a message; an ``out=`` destination of the wrong
+    shape or dtype, or a non-contiguous one, makes ops.ppo_eval raise AssertionError; nothing is launched, so the sentinel-filled outputs
+    stay as they were"""
     nA, bs, T, rows = shape
     inp = make_inputs(shape, True)
     good = run(inp, device, T, rows)
@@ -426,6 +428,8 @@ def check_bad_arguments(device, shape=(3, 5, 9, 36)):
     refused(ref, T=0)
     for k in INPUTS + ("stats", "step_stats", "workspace"):
         refused(ref, **{k: None})
+    assert_out_refused(lambda out: ops.ppo_eval(*(d[k] for k in INPUTS), T, rows=rows, clip=CLIP, huber_delta=HUBER, want=PER_ROW, out=out),
+                       bufs, ("stats", "step_stats", "ratio"))
     _sync(device)
     for k, (sent, buf, _) in bufs.items():
         assert torch.equal(buf.cpu(), sent), (k, "a refused call wrote an output")

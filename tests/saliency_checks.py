@@ -17,7 +17,7 @@ from iplan_amd import _lib as L
 from iplan_amd import ops
 from oracle import iplan_oracle as O
 from tests.oracle_checks import E32_FACTOR, _grad_err, _Log, _rel
-from tests.policy_trace_checks import _args, _bits, _codes, _e2e_args, _params, _sync, _worse, make_mac
+from tests.policy_trace_checks import _args, _bits, _codes, _e2e_args, _params, _sync, _worse, assert_out_refused, make_mac
 
 TOL = 1e-5
 M = 64
@@ -507,8 +507,9 @@ def check_host_api(device, dims=(2, 3, 3, 3, 5)):
 
 
 def check_bad_arguments(device, dims=(2, 3, 3, 3, 5)):
-    """7: each invalid descriptor is refused by the host-side check with a negative IPLAN_E* code and a message; nothing is launched,
-    so the sentinel-filled outputs stay as they were.  saliency() refuses layer_N = 2"""
+    """7: each invalid descriptor is refused by the host-side check with a negative IPLAN_E* code and a message; an ``out=`` destination
+    of the wrong shape or dtype, or a non-contiguous one, makes ops.saliency raise AssertionError; nothing is launched, so the
+    sentinel-filled outputs stay as they were.  saliency() refuses layer_N = 2"""
     case = get_case(dims, device)
     S = dims[2]
     good = case.run()
@@ -553,6 +554,11 @@ def check_bad_arguments(device, dims=(2, 3, 3, 3, 5)):
                               "act2_actor", "act1_critic", "act2_critic")}
     refused(ref, **none)
     refused(ref, which=1, **{k: None for k in none if k.endswith("critic") or k == "values"})          # only actor outputs, critics asked for
+
+    def with_out(out):                                                       # ops.saliency, called by the method with this ``out``
+        with _Injected(out=out):
+            case.run()
+    assert_out_refused(with_out, bufs, ("logp", "target_action", "entity_critic"))
     _sync(device)
     for k, (sent, buf, _) in bufs.items():
         assert torch.equal(buf.cpu(), sent), (k, "a refused call wrote an output")

@@ -19,7 +19,7 @@ from iplan_amd import _lib as L
 from iplan_amd import ops
 from oracle import iplan_oracle as O
 from tests.oracle_checks import _grad_err, _rel
-from tests.policy_trace_checks import _bits, _codes, _params, _sync, _worse
+from tests.policy_trace_checks import _bits, _codes, _params, _sync, _worse, assert_out_refused
 from tests.saliency_checks import M, TOL, _bound, _learner, _sentinels, _state_tensors, build_rows, entity_sums, get_case
 
 MIN_LAG_RATIO = 1e-3
@@ -490,7 +490,8 @@ def check_filled_weighting(device, dims=(2, 3, 4, 3, 5)):
 
 def check_bad_arguments(device, dims=(2, 3, 3, 3, 5)):
     """8: lags outside [0, S - 1] or not an int, and a slice with a step other than 1, raise ValueError; layer_N = 2 raises
-    NotImplementedError; at the C level each check of iplan_ac_saliency_lag returns its error code with a message and nothing is launched,
+    NotImplementedError; an ``out=`` destination of the wrong shape or dtype, or a non-contiguous one, makes ops.saliency_lag raise
+    AssertionError; at the C level each check of iplan_ac_saliency_lag returns its error code with a message and nothing is launched,
     so the sentinel-filled outputs stay as they were"""
     case = get_case(dims, device)
     S = dims[2]
@@ -559,6 +560,11 @@ def check_bad_arguments(device, dims=(2, 3, 3, 3, 5)):
     refused(x0, code=EALIGN, carry_s_row=M + 2)
     refused(x1, code=EALIGN, seed_s_row=M + 1)
     refused(x0, code=EALIGN, **{"base.act1_actor": x0.base.act1_actor + 4})
+
+    def with_out(out):                                                       # ops.saliency_lag, called by the method with this ``out``
+        with _Injected(out=out):
+            run(case)
+    assert_out_refused(with_out, bufs, ("carry_actor", "entity_critic", "target_action"))
     _sync(device)
     for k, (sent, buf, _) in bufs.items():
         assert torch.equal(buf.cpu(), sent), (k, "a refused call wrote an output")
