@@ -1340,6 +1340,55 @@ typedef struct {
 
 int iplan_pdec_saliency(const IplanPdecSaliencyArgs* args, iplan_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Neighbour knock-out (occlusion attribution of the GAT): every scene (net, b) is run once per JOB, forward only, with one entity's
+ * input row replaced (csrc/gat_knockout.hip).  A job is an entity index j in [0, N) or -1 (nothing knocked); the list jobs[J] is
+ * the same for every scene, duplicates are allowed, every slot is computed on its own by one 512-thread workgroup (grid n_nets*B*J).
+ * A slot's arithmetic is the inference form of iplan_gat_fwd (iplan_gat_trace's step), so latent_ko of job j carries the bits
+ * iplan_gat_fwd gives on a copy of the inputs with row j replaced; src0 / src1 are read in place and never written.
+ *   knock0 / knock1   which sources of entity j are replaced: source 0 by baseline0[d0], source 1 by baseline1[d1] (NULL = zeros)
+ *   hidden            the state every slot starts from, rows as iplan_gat_fwd's h_prev (NULL: zeros); entity j's row is NOT changed
+ *   noise             gumbel samples [n_nets, B, N, N-1, 2] contiguous, the same for every job of a scene; NULL = none
+ * Outputs, each optional (NULL = not wanted; at least one is), element (net, b, slot) at ptr + net*s_net + b*s_b + slot*s_job:
+ *   latent_ko [N, A]  the attention latent of the knocked scene (16-byte aligned, strides % 4 == 0)
+ *   attn_ko   [N, N]  the entity-indexed soft * hard map of the knocked scene, diagonal 0 (iplan_gat_trace's `attn`)
+ *   shift_sq  [N]     sum_c (latent_ko[i, c] - base[i, c])^2, c = 0 .. A-1 ascending, one lane per ego, every difference, product
+ *                     and sum rounded on its own (no fma; the plain fp32 host loop gives the same bits); no square root is taken.
+ *                     Needs `base`: rows (net, b, i) at base + net*base_s_net + b*base_s_b + i*A, written by an EARLIER launch.
+ * No atomics, no sums across workgroups: a slot's bits depend on its scene, its job and the arguments only.
+ * Refused: N outside [2, IPLAN_MAX_ENTITIES], J < 1, a job outside [-1, N-1] (checked on jobs_host), knock1 with d1 == 0, null or
+ * misaligned tensors, no output, shift_sq without base, more than 2^31 - 1 workgroups.
+ */
+typedef struct {
+    int32_t n_nets, B, N, d0, d1, J;
+    const float* src0;
+    int64_t src0_s_net, src0_s_b;
+    const float* src1;          /* may be NULL iff d1 == 0                                                 */
+    int64_t src1_s_net, src1_s_b;
+    const float* hidden;        /* or NULL                                                                 */
+    int64_t h_s_net, h_s_b;
+    const float* noise;
+    const float* params;        /* parameter arena, IPLAN_GAT_* offsets                                    */
+    int64_t params_s_net;
+    int64_t off[IPLAN_GAT_NPARAM];
+    float tau;
+    int32_t knock0, knock1;
+    const int32_t* jobs;        /* [J] device memory                                                       */
+    const int32_t* jobs_host;   /* the same values in host memory (argument checks)                        */
+    const float* baseline0;     /* [d0] or NULL                                                            */
+    const float* baseline1;     /* [d1] or NULL                                                            */
+    const float* base;          /* the latent of the scene with nothing knocked, or NULL                   */
+    int64_t base_s_net, base_s_b;
+    float* latent_ko;
+    int64_t lat_s_net, lat_s_b, lat_s_job;
+    float* attn_ko;
+    int64_t attn_s_net, attn_s_b, attn_s_job;
+    float* shift_sq;
+    int64_t shift_s_net, shift_s_b, shift_s_job;
+} IplanGatKnockoutArgs;
+
+int iplan_gat_knockout(const IplanGatKnockoutArgs* args, iplan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

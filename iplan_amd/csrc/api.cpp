@@ -25,7 +25,7 @@ extern "C" size_t iplan_sizeof(const char* name) {
     IPLAN_SZ(IplanWgradArgs) IPLAN_SZ(IplanPpoPrepareArgs) IPLAN_SZ(IplanPpoLossArgs) IPLAN_SZ(IplanPdecArgs) IPLAN_SZ(IplanBehArgs) IPLAN_SZ(IplanMlp3Args) IPLAN_SZ(IplanAdvNormArgs) IPLAN_SZ(IplanSeq2SeqArgs) IPLAN_SZ(IplanAcPackArgs) IPLAN_SZ(IplanP2pArgs) IPLAN_SZ(IplanIpcHandle) IPLAN_SZ(IplanAcXhatArgs) IPLAN_SZ(IplanAcFc1SplitArgs) IPLAN_SZ(IplanObsHistArgs) IPLAN_SZ(IplanSeq2SeqBwdArgs)
     IPLAN_SZ(IplanPredictArgs) IPLAN_SZ(IplanBehEvalArgs) IPLAN_SZ(IplanGatTraceArgs) IPLAN_SZ(IplanAcTraceArgs) IPLAN_SZ(IplanPpoEvalArgs)
     IPLAN_SZ(IplanAcSaliencyArgs) IPLAN_SZ(IplanAcSaliencyLagArgs) IPLAN_SZ(IplanEncSaliencyArgs) IPLAN_SZ(IplanGatSaliencyArgs)
-    IPLAN_SZ(IplanPdecSaliencyArgs)
+    IPLAN_SZ(IplanPdecSaliencyArgs) IPLAN_SZ(IplanGatKnockoutArgs)
 #undef IPLAN_SZ
     return 0;
 }

@@ -1,6 +1,7 @@
 // The GAT scene: one 512-thread workgroup runs GAT_Net.forward for the N <= 64 entities of one (agent-net, env) -- the four phases
-// csrc/gat.hip describes.  Included by gat.hip (the rollout / training launches) and gat_trace.hip (the forward-only walk over
-// the steps of an episode that also writes the attention out).  Needs api_util.h and wave_tile.h in front of it.
+// csrc/gat.hip describes.  Included by gat.hip (the rollout / training launches), gat_trace.hip (the forward-only walk over
+// the steps of an episode that also writes the attention out) and gat_knockout.hip (a scene run once per knocked-out entity).
+// Needs api_util.h and wave_tile.h in front of it.
 #pragma once
 
 namespace iplan {
@@ -53,8 +54,17 @@ __device__ __forceinline__ int gat_trace_opaque_lane(int v) {
     return v;
 }
 
-template <bool COH = false, bool FOLD = false, bool TRACE = false>
-__device__ __forceinline__ void gat_fwd_block(const IplanGatFwdArgs& a, int block, GatShared& sh, const GatTraceStep* tr = nullptr) {
+// KNOCK (gat_knockout.hip, on top of TRACE; `ko` = the workgroup's job): entity ko->j's input row is replaced as phase 1 loads it -- a
+// knocked source reads its baseline row instead (nullptr: zeros).  j = -1 knocks nothing.  Compiled out of every other instantiation.
+struct GatKnock {
+    int j;                              // the knocked entity, or -1
+    bool k0, k1;                        // which sources are knocked
+    const float *base0, *base1;         // [d0] / [d1] replacement rows, each may be nullptr (zeros)
+};
+
+template <bool COH = false, bool FOLD = false, bool TRACE = false, bool KNOCK = false>
+__device__ __forceinline__ void gat_fwd_block(const IplanGatFwdArgs& a, int block, GatShared& sh, const GatTraceStep* tr = nullptr,
+                                              const GatKnock* ko = nullptr) {
     auto& s_B = sh.B;
     auto& s_q = sh.q;
     auto& s_k = sh.k;
@@ -116,6 +126,14 @@ __device__ __forceinline__ void gat_fwd_block(const IplanGatFwdArgs& a, int bloc
                 r0 += tr->src0_off;
                 if (a.d1 > 0) r1 += tr->src1_off;
             }
+            [[maybe_unused]] bool z0 = false, z1 = false;     // KNOCK: this lane's row of source 0 / 1 reads as zeros
+            if constexpr (KNOCK) {
+                if (node == ko->j) {
+                    // (without a baseline the pointer keeps addressing the scene's own row, so it stays dereferenceable)
+                    if (ko->k0) { if (ko->base0) r0 = ko->base0; else z0 = true; }
+                    if (ko->k1 && a.d1 > 0) { if (ko->base1) r1 = ko->base1; else z1 = true; }
+                }
+            }
             const float* Wenc = P + a.off[IPLAN_GAT_ENC_W];
             const int KT = (D + 15) / 16;
             for (int T = 0; T < KT; ++T) {
@@ -123,8 +141,13 @@ __device__ __forceinline__ void gat_fwd_block(const IplanGatFwdArgs& a, int bloc
                 if (valid) {
                     for (int q = 0; q < 4; ++q) {
                         const int c = 16 * T + 4 * g + q;
-                        if (c < a.d0) x[q] = r0[c];
-                        else if (c < D) x[q] = r1[c - a.d0];
+                        if constexpr (KNOCK) {
+                            if (c < a.d0) x[q] = z0 ? 0.f : r0[c];
+                            else if (c < D) x[q] = z1 ? 0.f : r1[c - a.d0];
+                        } else {
+                            if (c < a.d0) x[q] = r0[c];
+                            else if (c < D) x[q] = r1[c - a.d0];
+                        }
                     }
                 }
                 acc0 = mma_block(wfrag(Wenc, D, GH, D, 0, 16 * T), x, acc0);

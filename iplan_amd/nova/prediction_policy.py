@@ -470,6 +470,212 @@ class Prediction_policy:
         res = {k: v.unflatten(1, (E, S)).permute(1, 2, 0, *range(3, v.dim() + 1)) for k, v in res.items()}
         return {k: v.cpu().numpy() for k, v in res.items()} if as_np else res
 
+    # ---------------------------------------------------------------------------- neighbour knock-out
+    def attention_knockout(self, history, behavior_latent=None, hidden=None, entities=None, sources=("history", "behavior"), baseline=None,
+                           noise=None, deterministic=True, tau=None, want=("shift",), forecast=False, pos=(1, 2), presence_col=0,
+                           max_workspace_mb=256):
+        """What becomes of ego i's social context, and of its forecast, if vehicle j were not there?  Occlusion (leave-one-out)
+        attribution of the GAT: for every row (env, step, agent) of ``history`` [E,S,nA,N,d] (with ``behavior_latent`` [E,S,nA,N,Z];
+        needed with ``GAT_use_behavior``, ignored without) and every entity j of ``entities`` (default: all N; duplicates allowed), the
+        GAT is run again with entity j's input row replaced (``iplan_gat_knockout``: one workgroup per row and j, inputs read in place).
+        ``hidden`` [E,S,nA,N,A] is the state each row starts from (None: zeros; for a recorded batch ``attention_latent[:, :-1]``); it
+        is held -- entity j's hidden row is not changed -- and nothing is carried through time, as in ``attention_saliency``.
+        ``sources``: what "not there" means -- ("history", "behavior") = the vehicle is unseen, ("behavior",) = the ego does not know
+        j's intent, ("history",) = only the observation row.  ``baseline``: None = zeros for both (for history the observation wrapper's
+        encoding of an unseen vehicle), or a pair (row [d] or None, row [Z] or None).  ``deterministic=True`` uses no gumbel noise and
+        draws nothing; otherwise ``noise`` [nA,E,S,N,N-1,2] (or a draw from torch's generator) is used for the base AND for every knocked
+        run (common random numbers).  ``tau``: None = the policy's own 0.01.
+        Returns a dict; pair tensors are indexed [ego i, knocked entity], J = len(entities):
+          ``latent`` [E,S,nA,N,A]           nothing knocked: bit for bit ``GAT_latent_update``'s on the same noise
+          ``latent_shift`` [E,S,nA,N,J]     with "shift" in ``want`` (the default): ||latent_ko[j][i] - latent[i]||_2, torch's sqrt of the
+                                            kernel's sum of squares (columns ascending, every product and sum rounded on its own)
+          ``knocked``                       the entity list (int64 numpy [J])
+          ``latent_ko`` [E,S,nA,J,N,A], ``attention_ko`` [E,S,nA,J,N,N]   with "latent_ko" / "attention_ko" in ``want``: the knocked
+                                            latents and entity-indexed soft * hard maps (``attention_map``'s ``attention`` on the modified copy)
+          ``summary`` float64 numpy [nA,2]  with "shift": after ONE read-back (without "shift" nothing is read back): [:, 0] the mean of latent_shift over pairs i != j with both present, [:, 1]
+                                            over i == j with i present (column ``presence_col`` of the history row non-zero; < 0: everything
+                                            counts); NaN where nothing counts
+        ``forecast=True`` sends the knocked latents through the decoder (``iplan_predict``; its start state is read in place and never
+        knocked, so the result isolates the social path) and adds ``pred`` [E,S,nA,N,P,d], bit for bit ``predict``'s, and
+        ``forecast_shift`` [E,S,nA,N,J,P]: the Euclidean distance over the ``pos`` columns between entity i's forecast with and without
+        j, formed in torch -- the squared differences of the columns added in ``pos`` order, then sqrt.
+        Rows and jobs are chunked so that what a chunk holds in flight stays under ``max_workspace_mb``; the bits do not depend on the
+        chunking.  numpy in -> numpy out, device tensors in -> device tensors out.  Parameters, gradients, optimiser state, carried
+        state and (with ``deterministic=True``) torch's generator are not touched.  Not covered: deleting an entity from the pair chain
+        (the row is replaced, which is what the environment would have shown), knocking the hidden state, continuation into the
+        actors and critics, effects carried through time, aggregation across data-parallel ranks."""
+        who = "attention_knockout"
+        as_np = isinstance(history, np.ndarray)
+        dev = self.device
+        hist = _as_dev(history, dev)
+        if hist.dim() != 5:
+            raise ValueError(f"{who}: history must be [E,S,nA,N,d], got {tuple(hist.shape)}")
+        E, S, nA, N, d = hist.shape
+        A, P = self.args.attention_dim, self.pred_length
+        if nA != self.n_agents or d != self.obs_shape or not 2 <= N <= ops.L.GAT_MAX_ENTITIES:
+            raise ValueError(f"{who}: history {tuple(hist.shape)} does not fit n_agents={self.n_agents}, obs width {self.obs_shape}, "
+                             f"2 <= N <= {ops.L.GAT_MAX_ENTITIES}")
+        sources = (sources,) if isinstance(sources, str) else tuple(sources)
+        if not sources or any(s not in ("history", "behavior") for s in sources):
+            raise ValueError(f"{who}: sources={sources} -- 'history', 'behavior' or both")
+        if "behavior" in sources and not self.args.GAT_use_behavior:
+            raise ValueError(f"{who}: sources={sources}, but this policy's GAT reads no behaviour latent (GAT_use_behavior is off)")
+        knock = ("history" in sources, "behavior" in sources)
+        want = tuple(want)
+        if any(k not in ("shift", "latent_ko", "attention_ko") for k in want):
+            raise ValueError(f"{who}: want={want} -- known: 'shift', 'latent_ko', 'attention_ko'")
+        if deterministic and noise is not None:
+            raise ValueError(f"{who}: noise was given together with deterministic=True")
+        tau = 0.01 if tau is None else float(tau)
+        if not tau > 0:
+            raise ValueError(f"{who}: tau={tau} must be positive")
+        if not isinstance(presence_col, (int, np.integer)) or presence_col >= d:
+            raise ValueError(f"{who}: presence_col={presence_col!r} outside the {d} columns")
+        if entities is None:
+            entities = range(N)
+        try:
+            jobs = list(entities)
+        except TypeError:
+            raise ValueError(f"{who}: entities={entities!r} -- None or a list of entity indices") from None
+        if not jobs or any(isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= j < N for j in jobs):
+            raise ValueError(f"{who}: entities={jobs} -- ints in [0, {N}), at least one")
+        jobs = [int(j) for j in jobs]
+        J = len(jobs)
+        pos = tuple(pos) if forecast else ()
+        if forecast and (not pos or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < d for c in pos)):
+            raise ValueError(f"{who}: pos={pos} -- columns in [0, {d}), at least one")
+        B = E * S
+        Z = self.args.latent_dim if self.args.GAT_use_behavior else 0
+        rows = [None, None]
+        if baseline is not None:
+            if not isinstance(baseline, (tuple, list)) or len(baseline) != 2:
+                raise ValueError(f"{who}: baseline -- None or a pair (row [{d}] or None, row [{Z}] or None)")
+            for s, (row, width) in enumerate(zip(baseline, (d, Z))):
+                if row is None:
+                    continue
+                row = _as_dev(torch.as_tensor(row), dev).contiguous()
+                if row.shape != (width,) or width == 0:
+                    raise ValueError(f"{who}: baseline[{s}] {tuple(row.shape)} != {(width,)}")
+                rows[s] = row
+        if hist.stride(4) != 1 or hist.stride(3) != d:
+            hist = hist.contiguous()
+        src0 = hist.permute(2, 0, 1, 3, 4).reshape(nA, B, N, d)                   # rows (agent, env * S + step): a view where the layout allows
+        lat = self._beh_latent(who, behavior_latent, (E, S, nA, N, Z))
+        if lat is not None:
+            if lat.stride(4) != 1 or lat.stride(3) != Z:
+                lat = lat.contiguous()
+            lat = lat.permute(2, 0, 1, 3, 4).reshape(nA, B, N, Z)
+        if hidden is None:
+            hid = torch.zeros(nA, B, N, A, dtype=torch.float32, device=dev)
+        else:
+            hid = _as_dev(hidden, dev)
+            if hid.shape != (E, S, nA, N, A):
+                raise ValueError(f"{who}: hidden {tuple(hid.shape)} != {(E, S, nA, N, A)}")
+            hid = hid.permute(2, 0, 1, 3, 4).reshape(nA, B, N, A).contiguous()
+        if noise is not None:
+            noise = _as_dev(noise, dev)
+            if noise.shape != (nA, E, S, N, N - 1, 2):
+                raise ValueError(f"{who}: noise {tuple(noise.shape)} != {(nA, E, S, N, N - 1, 2)}")
+            noise = noise.reshape(nA, B, N, N - 1, 2)
+        keep_shift, keep_lat, keep_attn = "shift" in want, "latent_ko" in want, "attention_ko" in want
+        if not (keep_shift or keep_lat or keep_attn or forecast):
+            raise ValueError(f"{who}: want={want} without forecast=True asks for nothing")
+        # what a chunk holds in flight, in bytes per row (all agents): the noise and the base latent (and forecast), and per (row, job)
+        # the knocked outputs (and forecasts)
+        per_row = 4 * nA * (2 * N * (N - 1) + N * A + (N * P * d if forecast else 0))
+        per_job = 4 * nA * ((N if keep_shift else 0) + (N * A if keep_lat or forecast else 0) + (N * N if keep_attn else 0) + (N * P * (d + 1) if forecast else 0))
+        budget = int(max_workspace_mb * (1 << 20))
+        if budget < per_row + per_job:
+            raise ValueError(f"{who}: max_workspace_mb={max_workspace_mb} is too small for one row and one job "
+                             f"({(per_row + per_job) / (1 << 20):.2f} MB)")
+        jc = min(J, (budget - per_row) // per_job)
+        rc = min(B, budget // (per_row + jc * per_job))
+        f32 = dict(dtype=torch.float32, device=dev)
+        res = {"latent": torch.empty(nA, B, N, A, **f32)}
+        if keep_shift:
+            res["shift_sq"] = torch.empty(nA, B, J, N, **f32)
+        if keep_lat:
+            res["latent_ko"] = torch.empty(nA, B, J, N, A, **f32)
+        if keep_attn:
+            res["attention_ko"] = torch.empty(nA, B, J, N, N, **f32)
+        if forecast:
+            res["pred"] = torch.empty(nA, B, N, P, d, **f32)
+            res["forecast_shift"] = torch.empty(nA, B, J, N, P, **f32)
+            row_off = (torch.arange(nA)[:, None] * src0.stride(0) + torch.arange(B)[None, :] * src0.stride(1)).to(torch.int64)
+            assert int(row_off.max()) + (N - 1) * src0.stride(2) + d <= ops._room(src0)
+            row_off = row_off.to(dev)
+        for b0 in range(0, B, rc):
+            b1 = min(B, b0 + rc)
+            nb = b1 - b0
+            nz = self._noise(noise, deterministic, nA, b0, b1, (N, N - 1, 2))
+            base = res["latent"][:, b0:b1]
+            s1 = None if lat is None else lat[:, b0:b1]
+            ops.gat_forward(self.gat_arena, src0[:, b0:b1], s1, hid[:, b0:b1], nz, tau=tau, out=base)      # the rollout's launch and bits
+            if forecast:
+                off_b = row_off[:, b0:b1].contiguous()
+                pb = ops.predict(self.dec_arena, src0, off_b, src0.stride(2), 0, base.reshape(nA, nb * N, A).contiguous(), N, P, d,
+                                 checked=True)["pred"]
+                pb = pb.view(nA, nb, N, P, d)
+                res["pred"][:, b0:b1] = pb
+            for j0 in range(0, J, jc):
+                j1 = min(J, j0 + jc)
+                nj = j1 - j0
+                out = {"shift_sq": res["shift_sq"][:, b0:b1, j0:j1]} if keep_shift else {}
+                if forecast:
+                    out["latent_ko"] = torch.empty(nA, nb, nj, N, A, **f32)     # contiguous: the decoder's h0
+                elif keep_lat:
+                    out["latent_ko"] = res["latent_ko"][:, b0:b1, j0:j1]
+                if keep_attn:
+                    out["attn_ko"] = res["attention_ko"][:, b0:b1, j0:j1]
+                ops.gat_knockout(self.gat_arena, src0[:, b0:b1], s1, hid[:, b0:b1], jobs[j0:j1], base=base if keep_shift else None, noise=None if deterministic else nz,
+                                 tau=tau, knock=knock, baseline=rows, want=tuple(out), out=out)
+                if forecast:
+                    if keep_lat:
+                        res["latent_ko"][:, b0:b1, j0:j1] = out["latent_ko"]
+                    off_j = off_b[:, :, None].expand(nA, nb, nj).reshape(nA, nb * nj).contiguous()
+                    pk = ops.predict(self.dec_arena, src0, off_j, src0.stride(2), 0, out["latent_ko"].view(nA, nb * nj * N, A), N, P, d,
+                                     checked=True)["pred"].view(nA, nb, nj, N, P, d)
+                    # the squared differences of the position columns, added in `pos` order, then sqrt
+                    acc = None
+                    for c in pos:
+                        diff = pk[..., c] - pb[:, :, None, :, :, c]
+                        acc = diff * diff if acc is None else acc + diff * diff
+                    res["forecast_shift"][:, b0:b1, j0:j1] = acc.sqrt()
+        shift = res.pop("shift_sq").sqrt() if keep_shift else None                 # [nA, B, J, N]
+
+        def rows_out(t, pair=False):                                               # [nA, B, ...] -> [E, S, nA, ...]; pair: [J, N, ..] -> [N, J, ..]
+            t = t.unflatten(1, (E, S)).permute(1, 2, 0, *range(3, t.dim() + 1))
+            return t.transpose(3, 4) if pair else t
+        final = {"latent": rows_out(res["latent"])}
+        if keep_shift:
+            final["latent_shift"] = rows_out(shift, pair=True)
+        if keep_lat:
+            final["latent_ko"] = rows_out(res["latent_ko"])
+        if keep_attn:
+            final["attention_ko"] = rows_out(res["attention_ko"])
+        if forecast:
+            final["pred"] = rows_out(res["pred"])
+            final["forecast_shift"] = rows_out(res["forecast_shift"], pair=True)
+        jn = np.asarray(jobs, dtype=np.int64)
+        if keep_shift:
+            # the two means per agent: ONE host read-back of the shifts and the presence flags
+            present = (src0[..., presence_col] != 0) if presence_col >= 0 else torch.ones(nA, B, N, dtype=torch.bool, device=dev)
+            host = torch.cat([shift, present[:, :, None, :].to(torch.float32)], dim=2).cpu().numpy().astype(np.float64)      # [nA, B, J + 1, N]
+            sh, pr = host[:, :, :J], host[:, :, J] != 0                                # [nA, B, J, N], [nA, B, N]
+            own = jn[:, None] == np.arange(N)[None, :]                                 # [J, N]: slot j knocks ego i itself
+            other = pr[:, :, None, :] & pr[:, :, jn][:, :, :, None] & ~own[None, None]
+            self_ = pr[:, :, None, :] & own[None, None]
+            summary = np.full((nA, 2), np.nan)
+            for col, m in enumerate((other, self_)):
+                cnt = m.sum(axis=(1, 2, 3)).astype(np.float64)
+                tot = np.where(m, sh, 0.0).sum(axis=(1, 2, 3))
+                summary[:, col] = np.where(cnt > 0, tot / np.maximum(cnt, 1.0), np.nan)
+        final = {k: (v.cpu().numpy() if as_np else v) for k, v in final.items()}
+        final["knocked"] = jn
+        if keep_shift:
+            final["summary"] = summary
+        return final
+
     # ---------------------------------------------------------------------------- prediction saliency
     def prediction_saliency(self, history_single, attention_hidden, behavior_latent=None, columns=(1, 2), horizons=None, target=None,
                             noise=None, deterministic=True, social=None, gate="through", want=("summary",), presence_col=0,

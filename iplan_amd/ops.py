@@ -220,6 +220,90 @@ def gat_trace_args(arena, src0, src1=None, hidden0=None, noise=None, tau=0.01, w
     return a, res
 
 
+GAT_KNOCKOUT_OUTPUTS = ("latent_ko", "attn_ko", "shift_sq")
+
+
+def gat_knockout(arena, src0, src1, hidden, jobs, base=None, noise=None, tau=0.01, knock=(True, True), baseline=(None, None),
+                 want=("shift_sq",), out=None, lib=None):
+    """Every scene run once per job with one entity's input row replaced (iplan_gat_knockout), forward only.  src0 [n_nets,B,N,d0],
+    src1 [n_nets,B,N,d1] or None, hidden [n_nets,B,N,A] or None (zeros): views whose first two dims may be strided arbitrarily, read in
+    place.  ``jobs``: J entity indices in [0, N), or -1 for "nothing knocked" (duplicates allowed), shared by all scenes.  ``knock``:
+    which of (src0, src1) is replaced in the knocked row, by ``baseline`` = (row [d0] or None, row [d1] or None), None = zeros.
+    ``noise`` [n_nets,B,N,N-1,2] contiguous or None (no gumbel term): the same samples for every job of a scene.  ``want``: which of
+    latent_ko [n_nets,B,J,N,A], attn_ko [n_nets,B,J,N,N] (entity-indexed soft * hard, diagonal 0), shift_sq [n_nets,B,J,N] (sum_c
+    (latent_ko - base)^2; needs ``base`` [n_nets,B,N,A], first two dims strided, produced by an earlier launch) to produce; ``out``:
+    optional dict of destination views for some of them (the same layouts, first three dims strided).  Everything the kernel will
+    touch is bounds-checked here, on the host.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res, keep = gat_knockout_args(arena, src0, src1, hidden, jobs, base, noise, tau, knock, baseline, want, out)
+    n_nets, B, N, d0 = src0.shape
+    _launch("gat_knockout_kernel", lambda: lib.call("iplan_gat_knockout", a, L.current_stream(src0.device)),
+            work=a.J * _gat_flops(n_nets, B, N, d0 + a.d1, 32))
+    res["_keep"] = keep
+    return res
+
+
+def gat_knockout_args(arena, src0, src1, hidden, jobs, base=None, noise=None, tau=0.01, knock=(True, True), baseline=(None, None),
+                      want=("shift_sq",), out=None):
+    """The descriptor of a ``gat_knockout`` launch, its output tensors and what must stay alive until the launch has been queued,
+    checked but not launched: (IplanGatKnockoutArgs, dict, list)."""
+    n_nets, B, N, d0 = src0.shape
+    d1 = 0 if src1 is None else src1.shape[-1]
+    A = 32
+    dev = src0.device
+    want = tuple(want)
+    assert want and all(k in GAT_KNOCKOUT_OUTPUTS for k in want), want
+    jobs = [int(j) for j in jobs]
+    J = len(jobs)
+    assert J >= 1 and all(-1 <= j < N for j in jobs), (jobs, N)
+    k0, k1 = bool(knock[0]), bool(knock[1])
+    assert not (k1 and d1 == 0), "source 1 is to be knocked, but there is none"
+    a = L.GatKnockoutArgs()
+    a.n_nets, a.B, a.N, a.d0, a.d1, a.J = n_nets, B, N, d0, d1, J
+    a.src0 = src0.data_ptr()
+    a.src0_s_net, a.src0_s_b, _ = _nbs_strides(src0.unsqueeze(2), N * d0, "src0")
+    if src1 is not None:
+        assert src1.shape[:3] == (n_nets, B, N) and src1.device == dev, src1.shape
+        a.src1 = src1.data_ptr()
+        a.src1_s_net, a.src1_s_b, _ = _nbs_strides(src1.unsqueeze(2), N * d1, "src1")
+    if hidden is not None:
+        assert hidden.shape == (n_nets, B, N, A) and hidden.device == dev, hidden.shape
+        a.hidden = hidden.data_ptr()
+        a.h_s_net, a.h_s_b, _ = _nbs_strides(hidden.unsqueeze(2), N * A, "hidden")
+    if noise is not None:
+        assert noise.is_contiguous() and noise.shape == (n_nets, B, N, N - 1, 2) and noise.dtype == torch.float32 and noise.device == dev, noise.shape
+        a.noise = noise.data_ptr()
+    if base is not None:
+        assert base.shape == (n_nets, B, N, A) and base.device == dev, base.shape
+        a.base = base.data_ptr()
+        a.base_s_net, a.base_s_b, _ = _nbs_strides(base.unsqueeze(2), N * A, "base")
+    assert "shift_sq" not in want or base is not None, "shift_sq needs base, the latent with nothing knocked"
+    j_host = (C.c_int32 * J)(*jobs)
+    j_dev = torch.tensor(jobs, dtype=torch.int32, device=dev)
+    a.jobs, a.jobs_host = j_dev.data_ptr(), C.cast(j_host, C.c_void_p)
+    a.knock0, a.knock1 = int(k0), int(k1)
+    keep = [src0, src1, hidden, noise, base, j_host, j_dev]
+    for which, (row, d) in enumerate(zip(baseline, (d0, d1))):
+        if row is not None:
+            assert row.shape == (d,) and row.dtype == torch.float32 and row.is_contiguous() and row.device == dev, (which, row.shape)
+            setattr(a, f"baseline{which}", row.data_ptr())
+            keep.append(row)
+    a.params = arena.data.data_ptr()
+    a.params_s_net = arena.net_stride
+    for i, k in enumerate(L.GAT_PARAM_ORDER):
+        a.off[i] = arena.off(k)
+    a.tau = tau
+    res = {}
+    pre = {"latent_ko": "lat", "attn_ko": "attn", "shift_sq": "shift"}
+    for k in want:
+        inner = {"latent_ko": (N, A), "attn_ko": (N, N), "shift_sq": (N,)}[k]
+        t, *s = _dest_nbs(out, res, k, (n_nets, B, J), inner, dev)
+        setattr(a, k, t.data_ptr())
+        for name, v in zip(("net", "b", "job"), s):
+            setattr(a, f"{pre[k]}_s_{name}", v)
+    return a, res, keep
+
+
 GAT_SALIENCY_OUTPUTS = ("grad", "pair_gl1", "pair_gxi", "input_grad", "hidden_grad")
 
 
