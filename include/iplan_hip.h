@@ -1389,6 +1389,58 @@ typedef struct {
 
 int iplan_gat_knockout(const IplanGatKnockoutArgs* args, iplan_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Policy knock-out (occlusion attribution of the actors and critics): every row (e, s, agent) of a recorded batch is run once per
+ * JOB, forward only -- LN(F) -> fc1 -> act -> LN -> fc2 -> act -> LN -> GRU cell (state given, held) -> LN -> head -> masked softmax | V
+ * -- with one entity's columns of the selected per-entity sources replaced AS THE FEATURES ARE GATHERED (csrc/policy_knockout.hip,
+ * ac_kmap_ko.h); nothing is copied or modified in memory.  `base` describes the rows exactly as for iplan_ac_saliency (feat, nets, h_*,
+ * avail, target, packed_*); of its outputs logp, values and target_out [n_agents, E*S] receive the row's BASE result (nothing knocked)
+ * and the a* that was used, the others must be NULL.  A job is an entity index in [0, N) or -1 (nothing knocked); jobs[J] is the same
+ * for every row, duplicates are allowed.
+ *   knock[k]      source k's columns of the job's entity are replaced: entry f of the row's source block belongs to entity f / w[k] and
+ *                 becomes baseline[k][f - e*w[k]] (baseline[k] NULL: 0).  The replacement precedes LayerNorm(F): the statistics are
+ *                 those of the modified row.  The one-hots are never knocked.
+ *   override[k]   instead of the row's own vector, job q of row (e, s) of agent `net` reads source k from
+ *                 override[k] + q*ov_s_job[k] + net*ov_s_net[k] + e*ov_s_chain[k] + s*ov_s_step[k] + entity*ov_s_ent[k] + column
+ *                 (innermost axis contiguous).  An overridden source is taken as given: it is not knocked as well, for any job.
+ * a*: the row's entry of base.target (base.target_all), or the BASE result's argmax where that is -1 -- one action per row, the same
+ * for every job of it.
+ * Work: one wave per tile of 16 columns = the 15 jobs 15*jt .. 15*jt + 14 of ONE row and, in column 15, the row's base result, which
+ * every tile carries; ceil(J / 15) tiles per row, four tiles per workgroup, grid over tiles x agents x nets.  The arithmetic of a
+ * column is iplan_ac_saliency's forward half (fc1 on v_mfma_f32_16x16x4_f32, the same k-tile order and partial sums of 8 k-tiles).
+ * Outputs, each optional, contiguous, of the nets base.which selects, slot (net, row, job) at index (net*E*S + row)*J + job:
+ *   probs_ko  [.., n_actions]   logp_ko (of a*), values_ko, greedy_ko (int64, lowest index on ties)
+ *   kl     = sum over the available actions, ascending, of p_base * (logp_base - logp_ko); every term rounded on its own (no fma)
+ *   dlogp  = logp_ko - logp_base,  dvalue = V_ko - V_base      formed by one lane per (row, job) from its tile's base column
+ *   probs_base [n_agents, E*S, n_actions], greedy_base [n_agents, E*S] int64    the base result (with base.logp / values / target_out)
+ * At least one output must be asked for.  A slot whose gathered values equal the row's has kl = dlogp = dvalue = 0.0 and the base's
+ * bits.  No atomics, no sums across columns: a slot's bits do not depend on its lane, tile, workgroup, the other jobs, J or on which
+ * outputs were asked for.  Refused: what iplan_ac_saliency refuses of the rows, J < 1, a job outside [-1, N) (checked on jobs_host),
+ * knock or override on an absent source, negative override strides, E*S*ceil(J/15) tiles beyond 2^31 / 16, a base output other than
+ * logp / values / target_out.
+ */
+typedef struct {
+    IplanAcSaliencyArgs base;
+    int32_t J;
+    int32_t knock[3];
+    const int32_t* jobs;        /* [J] device memory                                                       */
+    const int32_t* jobs_host;   /* the same values in host memory (argument checks)                        */
+    const float* baseline[3];   /* [w[k]] or NULL (zeros)                                                  */
+    const float* override_src[3];
+    int64_t ov_s_job[3], ov_s_net[3], ov_s_chain[3], ov_s_step[3], ov_s_ent[3];
+    float* probs_base;
+    int64_t* greedy_base;
+    float* probs_ko;
+    float* logp_ko;
+    float* values_ko;
+    int64_t* greedy_ko;
+    float* kl;
+    float* dlogp;
+    float* dvalue;
+} IplanAcKnockoutArgs;
+
+int iplan_ac_knockout(const IplanAcKnockoutArgs* args, iplan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

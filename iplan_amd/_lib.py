@@ -54,7 +54,7 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_ac_xhat_pack", "iplan_ac_fc1_split_fwd", "iplan_ac_bwd_fc1_split",
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
                 "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
-                "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout"]
+                "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -526,6 +526,16 @@ class AcSaliencyLagArgs(C.Structure):
     ]
 
 
+class AcKnockoutArgs(C.Structure):
+    _fields_ = [
+        ("base", AcSaliencyArgs), ("J", i32), ("knock", i32 * 3), ("jobs", fp), ("jobs_host", fp),
+        ("baseline", fp * 3), ("override_src", fp * 3),
+        ("ov_s_job", i64 * 3), ("ov_s_net", i64 * 3), ("ov_s_chain", i64 * 3), ("ov_s_step", i64 * 3), ("ov_s_ent", i64 * 3),
+        ("probs_base", fp), ("greedy_base", fp), ("probs_ko", fp), ("logp_ko", fp), ("values_ko", fp), ("greedy_ko", fp),
+        ("kl", fp), ("dlogp", fp), ("dvalue", fp),
+    ]
+
+
 # ---- FC behaviour ablation -------------------------------------------------------------------------------
 class Mlp3Args(C.Structure):
     _fields_ = [
@@ -565,4 +575,5 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanGatTraceArgs": GatTraceArgs, "IplanAcTraceArgs": AcTraceArgs, "IplanPpoEvalArgs": PpoEvalArgs,
                   "IplanAcSaliencyArgs": AcSaliencyArgs, "IplanAcSaliencyLagArgs": AcSaliencyLagArgs,
                   "IplanEncSaliencyArgs": EncSaliencyArgs, "IplanGatSaliencyArgs": GatSaliencyArgs,
-                  "IplanPdecSaliencyArgs": PdecSaliencyArgs, "IplanGatKnockoutArgs": GatKnockoutArgs}
+                  "IplanPdecSaliencyArgs": PdecSaliencyArgs, "IplanGatKnockoutArgs": GatKnockoutArgs,
+                  "IplanAcKnockoutArgs": AcKnockoutArgs}

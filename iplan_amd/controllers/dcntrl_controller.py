@@ -438,6 +438,173 @@ class DcntrlMAC:
                     out[net + "_" + k] = res[k + "_" + net].permute(1, 2, 0, 3)
         return {k: (v if k == "sources" else v.cpu().numpy()) for k, v in out.items()} if as_np else out
 
+    KNOCKOUT_WANT = ("kl", "probs_ko", "logp_ko", "values_ko", "summary")
+
+    def knockout(self, batch, entities=None, sources=None, baseline=None, override=None, target="recorded", which="both", hidden=None,
+                 steps=None, want=("kl",), presence_col=0, max_workspace_mb=256):
+        """Would this agent have acted differently, and would its critic have valued the state differently, if vehicle j had not been
+        there?  The finite answer ``saliency`` cannot give (LayerNorm(F) rescales every other column when an entity's columns go, and the
+        masked softmax flips near a tie): every row (e, s, agent) is run once per entity j of ``entities`` with j's columns of the selected
+        ``sources`` replaced as the kernel gathers the features (ops.policy_knockout) -- the batch is read in place and not copied.
+        ``batch``, ``target``, ``which``, ``hidden`` and ``steps`` as for ``saliency``: the GRU state of a row is the recorded one (or
+        ``hidden``), given and held constant; nothing is carried through time.  With ``target="greedy"`` (or -1 entries) a* is the
+        argmax of the row with NOTHING knocked, the same action for every j.
+        ``entities``: entity indices in [0, N), None = all N; -1 = "nothing knocked" is allowed.  ``sources``: which of the names in
+        ``_widths()`` are knocked, None = all.  ``baseline``: None (zeros) or a dict name -> row [w] that replaces the entity's columns.
+        ``override``: a dict name -> tensor [E, S, nA, J, N, w] over the selected steps (any strides, innermost contiguous, read in
+        place): job j of row (e, s, a) takes that source from override[e, s, a, j] instead of the batch; an overridden source is taken
+        as given and not knocked as well.  This is how ``Prediction_policy.attention_knockout(..., want=("latent_ko",))`` continues into
+        the policy.  The rollout writes ``attention_latent[:, t + 1] = GAT(history[:, t + 1], attention_latent[:, t], behavior_latent[:, t])``,
+        so the ``latent_ko`` [E, S, nA, J, N, A] of ``attention_knockout(history[:, t0 + 1:t1 + 1], behavior_latent[:, t0:t1],
+        attention_latent[:, t0:t1], want=("latent_ko",))`` is what ``attention_latent[:, t0 + 1:t1 + 1]`` would have held without entity j:
+        ``knockout(batch, steps=slice(t0 + 1, t1 + 1), override={"attention_latent": latent_ko})`` with the same entity list closes
+        "vehicle j unseen -> social context of every ego -> action and value" (INTEGRATION.md 1).
+        Returns a dict; pair axes [E, S, nA, J]:
+          kl = KL(pi_base || pi_ko), dlogp = logp_ko - logp_base (of a*), dvalue = V_ko - V_base, greedy (int64, lowest index on ties),
+          flip = greedy != the base row's greedy;  base logp, values, target_action, greedy_base [E, S, nA] and probs [E, S, nA,
+          n_actions];  knocked (the entity list), sources (the names that were knocked);
+          probs_ko [.., n_actions], logp_ko, values_ko with those names in ``want``;
+          entity_kl, entity_abs_dvalue, flip_rate [nA, J] float64 with "summary" in ``want``: means over the rows with weight
+          ``batch["filled"]``, over the rows where the knocked entity is present (``history[..., j, presence_col] != 0``; every row
+          for job -1, and for every job with ``presence_col`` < 0, as in ``attention_knockout``), 0 where no such row exists; formed on
+          the device in float64, in environment order, from the per-pair outputs.
+        ``want`` only ADDS results: kl, dlogp, dvalue, greedy and flip are always returned (and always counted in the chunk sizes), so
+        the default ("kl",) and () ask for the same.
+        Those of a net ``which`` leaves out are missing.  Rows and jobs are chunked so that one launch's outputs stay below
+        ``max_workspace_mb``; chunked and unchunked calls give the same bits.  Where the replaced values equal the originals kl, dlogp
+        and dvalue are exactly 0.  Unavailable actions have probability exactly 0 and contribute nothing to kl; a row with no
+        available action is uniform (``policy_trace``'s convention) and has kl = 0.  Device tensors in -> device tensors out, numpy in
+        -> numpy out.  Draws from no generator; parameters, gradient entries, optimiser state, ``hidden_states`` and the batch are not
+        touched.  Not covered: layer_N / recurrent_N other than 1, knocking the GRU state, effects carried through time."""
+        a = self.args
+        if a.layer_N != 1 or a.recurrent_N != 1:
+            raise NotImplementedError("knockout covers layer_N = recurrent_N = 1 only")
+        want = tuple(want)
+        if any(k not in self.KNOCKOUT_WANT for k in want):
+            raise ValueError(f"knockout: want={want!r} names something other than {self.KNOCKOUT_WANT}")
+        if which not in ("actor", "critic", "both"):
+            raise ValueError(f"knockout: which={which!r}")
+        nA, M, N = self.n_agents, a.rnn_hidden_dim, a.max_vehicle_num
+        widths = self._widths()
+        names = [k for k, _ in widths]
+        ents = list(range(N)) if entities is None else [int(j) for j in np.asarray(entities).reshape(-1)]
+        if not ents or any(not -1 <= j < N for j in ents):
+            raise ValueError(f"knockout: entities={ents!r} must be a non-empty list of indices in [-1, {N})")
+        srcs = tuple(names) if sources is None else tuple(sources)
+        if not srcs or any(k not in names for k in srcs):
+            raise ValueError(f"knockout: sources={srcs!r} is not a non-empty subset of {names!r}")
+        for what, d in (("baseline", baseline), ("override", override)):
+            if d is not None and (not isinstance(d, dict) or any(k not in names for k in d)):
+                raise ValueError(f"knockout: {what} is a dict whose keys are among {names!r}")
+        T1 = batch["history"].shape[1]
+        one = isinstance(steps, (int, np.integer))
+        if steps is None:
+            t0, S = 0, T1
+        elif one:
+            t0, S = int(steps), 1
+        else:
+            t0, t1, stride = steps.indices(T1)
+            if stride != 1 or t1 - t0 < 1:
+                raise ValueError("knockout: steps is None, an int or a non-empty slice with step 1")
+            S = t1 - t0
+        if not isinstance(presence_col, (int, np.integer)) or presence_col >= widths[0][1]:
+            raise ValueError(f"knockout: presence_col={presence_col!r} outside the history width {widths[0][1]} (< 0: every row counts)")
+        if not max_workspace_mb > 0:
+            raise ValueError("knockout: max_workspace_mb must be positive")
+        r = self._rows(batch, t0, S)
+        E, as_np, dev = r.E, r.as_np, r.dev
+        J = len(ents)
+        if hidden is None:
+            ha, hc = r.field("rnn_states_actors", th.float32)[:, r.sl], r.field("rnn_states_critics", th.float32)[:, r.sl]
+        else:
+            ha, hc = (dev(h, th.float32) for h in hidden)
+        assert ha.shape == hc.shape == (E, S, nA, M), (ha.shape, hc.shape, (E, S, nA, M))
+        if ha.stride() != hc.stride() or ha.stride(3) != 1:
+            ha, hc = ha.contiguous(), hc.contiguous()
+        tgt, tgt_strides = self._target(r, target)
+        w = {"actor": 0, "critic": 1, "both": 2}[which]
+        base_rows, over = [], []
+        for k, wd in widths:
+            row = None if baseline is None or baseline.get(k) is None else dev(baseline[k], th.float32).contiguous()
+            if row is not None and row.shape != (wd,):
+                raise ValueError(f"knockout: baseline[{k!r}] has shape {tuple(row.shape)}, the source's width is {wd}")
+            base_rows.append(row)
+            ov = None if override is None or override.get(k) is None else dev(override[k], th.float32)
+            if ov is not None:
+                if ov.shape != (E, S, nA, J, N, wd):
+                    raise ValueError(f"knockout: override[{k!r}] has shape {tuple(ov.shape)}, not {(E, S, nA, J, N, wd)}")
+                if min(ov.stride()) < 0 or (wd > 1 and ov.stride(5) != 1):
+                    ov = ov.contiguous()
+            over.append(ov)
+        knock = tuple(k in srcs for k in names)
+        extra = tuple(k for k in ("probs_ko", "logp_ko", "values_ko") if k in want)
+        ask = ("kl", "dlogp", "dvalue", "greedy_ko") + extra
+        # chunks: whole environments x a range of jobs, one launch's per-pair outputs below the budget
+        pair_bytes = nA * S * (4 * 3 + 8 + 4 * (("logp_ko" in extra) + ("values_ko" in extra) + a.n_actions * ("probs_ko" in extra)))
+        budget = int(max_workspace_mb * 2 ** 20)
+        Jc = max(1, min(J, budget // pair_bytes))
+        Ec = max(1, min(E, budget // (pair_bytes * Jc)))
+        whole = Ec == E and Jc == J
+        res = {}
+        for e0 in range(0, E, Ec):
+            es = slice(e0, min(E, e0 + Ec))
+            En = es.stop - es.start
+            spec = r.spec
+            if not whole:
+                spec = ops.AcFeatureSpec(spec.N, [(t[es], wd, sn, sr) for t, wd, sn, sr in spec.sources], n_actions=spec.n_actions,
+                                         last_action=None if spec.last_action is None else spec.last_action[es], la_strides=spec.la_strides,
+                                         n_id=spec.n_id, T=S, T_phys=spec.T_phys)
+            for j0 in range(0, J, Jc):
+                js = slice(j0, min(J, j0 + Jc))
+                part = ops.policy_knockout(self.actor_arena, self.critic_arena, w, spec, En, S, nA, ents[js], h_actor=ha[es], h_critic=hc[es],
+                                           h_strides=_esn(ha), avail=r.avail[es], avail_strides=_esn(r.avail),
+                                           target=None if tgt is None else tgt[es], target_strides=tgt_strides, target_all=-1,
+                                           n_actions=a.n_actions, knock=knock, baseline=base_rows,
+                                           override=[None if ov is None else ov[es, :, :, js].permute(2, 0, 1, 3, 4, 5) for ov in over],
+                                           want=ask + (("base",) if j0 == 0 else ()), packed=r.packed)
+                if whole:
+                    res = part
+                    continue
+                for k, v in part.items():
+                    pairwise = k in ask
+                    if k not in res:
+                        shape = list(v.shape)
+                        shape[1] = E
+                        if pairwise:
+                            shape[3] = J
+                        res[k] = th.empty(shape, dtype=v.dtype, device=v.device)
+                    if pairwise:
+                        res[k][:, es, :, js] = v
+                    else:
+                        res[k][:, es] = v
+        out = {"knocked": tuple(ents), "sources": srcs}
+        meta = tuple(out)
+        rename = {"greedy_ko": "greedy", "greedy": "greedy_base"}
+        for k, v in res.items():
+            out[rename.get(k, k)] = v.permute(1, 2, 0, *range(3, v.dim()))
+        if "greedy" in out:
+            out["flip"] = out["greedy"] != out["greedy_base"].unsqueeze(-1)
+        if "summary" in want:
+            filled = dev(batch["filled"]).reshape(-1, T1)[:, r.sl].to(th.float64)                # [E, S]
+            hist = r.field("history", th.float32)[:, r.sl]                                        # [E, S, nA, N, d]
+            idx = th.as_tensor([max(j, 0) for j in ents], device=self.device)
+            pres = th.as_tensor([j < 0 or presence_col < 0 for j in ents], device=self.device).expand(*hist.shape[:3], J)
+            if presence_col >= 0:
+                pres = pres | (hist[..., presence_col].index_select(3, idx) != 0)                 # [E, S, nA, J]
+            wt = filled[:, :, None, None] * pres                                                  # [E, S, nA, J]
+            cols = [(name, v) for name, v in (("entity_kl", out.get("kl")), ("entity_abs_dvalue", None if "dvalue" not in out else out["dvalue"].abs()),
+                                              ("flip_rate", out.get("flip"))) if v is not None]
+            per_env = th.stack([(v.to(th.float64) * wt).sum(1) for _, v in cols] + [wt.sum(1)])   # [n + 1, E, nA, J]
+            tot = th.zeros(len(cols) + 1, nA, J, dtype=th.float64, device=self.device)
+            for e in range(E):                                                                    # environment order
+                tot += per_env[:, e]
+            for k, (name, _) in enumerate(cols):
+                out[name] = th.where(tot[-1] > 0, tot[k] / tot[-1].clamp_min(1e-300), th.zeros_like(tot[k]))
+        if one:
+            keep = meta + ("entity_kl", "entity_abs_dvalue", "flip_rate")
+            out = {k: (v if k in keep else v[:, 0]) for k, v in out.items()}
+        return {k: (v if k in meta else v.cpu().numpy()) for k, v in out.items()} if as_np else out
+
     def get_value_ippo(self, agent_id, obs, rnn_states_critic):
         """controllers/dcntrl_controller.py:61-68."""
         obs_in = obs.reshape(-1, 1, obs.shape[-1])

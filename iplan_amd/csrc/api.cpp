@@ -1,5 +1,6 @@
 // C-ABI bookkeeping: version + thread-local error string; the argument checks of iplan_ppo_eval (kernels: ppo_eval.hip) and of
-// iplan_ac_saliency (kernel: policy_saliency.hip) and of iplan_ac_saliency_lag (kernels: policy_saliency_lag.hip).
+// iplan_ac_saliency (kernel: policy_saliency.hip), of iplan_ac_saliency_lag (kernels: policy_saliency_lag.hip) and of iplan_ac_knockout
+// (kernel: policy_knockout.hip).
 #include <cstring>
 
 #include "api_util.h"
@@ -12,6 +13,7 @@ char* error_buffer() {
 int ppo_eval_launch(const IplanPpoEvalArgs& a, hipStream_t stream);   // ppo_eval.hip
 int ac_saliency_launch(const IplanAcSaliencyArgs& a, hipStream_t stream);   // policy_saliency.hip
 int ac_saliency_lag_launch(const IplanAcSaliencyLagArgs& a, hipStream_t stream);   // policy_saliency_lag.hip
+int ac_knockout_launch(const IplanAcKnockoutArgs& a, hipStream_t stream);   // policy_knockout.hip
 }  // namespace iplan
 
 extern "C" const char* iplan_last_error(void) { return iplan::error_buffer(); }
@@ -25,7 +27,7 @@ extern "C" size_t iplan_sizeof(const char* name) {
     IPLAN_SZ(IplanWgradArgs) IPLAN_SZ(IplanPpoPrepareArgs) IPLAN_SZ(IplanPpoLossArgs) IPLAN_SZ(IplanPdecArgs) IPLAN_SZ(IplanBehArgs) IPLAN_SZ(IplanMlp3Args) IPLAN_SZ(IplanAdvNormArgs) IPLAN_SZ(IplanSeq2SeqArgs) IPLAN_SZ(IplanAcPackArgs) IPLAN_SZ(IplanP2pArgs) IPLAN_SZ(IplanIpcHandle) IPLAN_SZ(IplanAcXhatArgs) IPLAN_SZ(IplanAcFc1SplitArgs) IPLAN_SZ(IplanObsHistArgs) IPLAN_SZ(IplanSeq2SeqBwdArgs)
     IPLAN_SZ(IplanPredictArgs) IPLAN_SZ(IplanBehEvalArgs) IPLAN_SZ(IplanGatTraceArgs) IPLAN_SZ(IplanAcTraceArgs) IPLAN_SZ(IplanPpoEvalArgs)
     IPLAN_SZ(IplanAcSaliencyArgs) IPLAN_SZ(IplanAcSaliencyLagArgs) IPLAN_SZ(IplanEncSaliencyArgs) IPLAN_SZ(IplanGatSaliencyArgs)
-    IPLAN_SZ(IplanPdecSaliencyArgs) IPLAN_SZ(IplanGatKnockoutArgs)
+    IPLAN_SZ(IplanPdecSaliencyArgs) IPLAN_SZ(IplanGatKnockoutArgs) IPLAN_SZ(IplanAcKnockoutArgs)
 #undef IPLAN_SZ
     return 0;
 }
@@ -124,4 +126,34 @@ extern "C" int iplan_ac_saliency_lag(const IplanAcSaliencyLagArgs* x, iplan_stre
         (x->carry_s_row & 3))
         return fail(IPLAN_EALIGN, "iplan_ac_saliency_lag: seed and carry must be 16-byte aligned, their row strides multiples of 4");
     return ac_saliency_lag_launch(*x, (hipStream_t)stream);
+}
+
+extern "C" int iplan_ac_knockout(const IplanAcKnockoutArgs* k, iplan_stream_t stream) {
+    using namespace iplan;
+    if (!k) return fail(IPLAN_EINVAL, "iplan_ac_knockout: null args");
+    const IplanAcSaliencyArgs* a = &k->base;
+    if (const int rc = saliency_check(a, false)) return rc;                  // (the row description: iplan_ac_saliency's rules)
+    if (a->entity_actor || a->entity_critic || a->input_grad_actor || a->input_grad_critic || a->act1_actor || a->act2_actor || a->act1_critic ||
+        a->act2_critic)
+        return fail(IPLAN_EINVAL, "iplan_ac_knockout: of base's outputs only logp, values and target_out (the base result) are written");
+    if (k->J < 1) return fail(IPLAN_EINVAL, "iplan_ac_knockout: J=%d, at least one job is needed", k->J);
+    if (!k->jobs || !k->jobs_host) return fail(IPLAN_EINVAL, "iplan_ac_knockout: the job list is missing (device and host copy)");
+    for (int s = 0; s < k->J; ++s)
+        if (k->jobs_host[s] < -1 || k->jobs_host[s] >= a->feat.N)
+            return fail(IPLAN_EINVAL, "iplan_ac_knockout: job %d = %d outside [-1,%d)", s, k->jobs_host[s], a->feat.N);
+    const int64_t tiles_per_row = (k->J + 14) / 15;
+    if ((int64_t)a->E * a->S * tiles_per_row > 0x7fffffff / 16)
+        return fail(IPLAN_EINVAL, "iplan_ac_knockout: E * S * ceil(J / 15) = %lld tiles are too many", (long long)a->E * a->S * tiles_per_row);
+    for (int s = 0; s < 3; ++s) {
+        if (k->knock[s] && a->feat.w[s] == 0) return fail(IPLAN_EINVAL, "iplan_ac_knockout: source %d is to be knocked, but it is absent", s);
+        if (k->baseline[s] && a->feat.w[s] == 0) return fail(IPLAN_EINVAL, "iplan_ac_knockout: a baseline for the absent source %d", s);
+        if (k->override_src[s] && a->feat.w[s] == 0) return fail(IPLAN_EINVAL, "iplan_ac_knockout: an override for the absent source %d", s);
+        if (k->override_src[s] && (k->ov_s_job[s] < 0 || k->ov_s_net[s] < 0 || k->ov_s_chain[s] < 0 || k->ov_s_step[s] < 0 || k->ov_s_ent[s] < 0))
+            return fail(IPLAN_EINVAL, "iplan_ac_knockout: negative override stride of source %d", s);
+    }
+    bool any = false;
+    if (a->which != 1) any = any || a->logp || a->target_out || k->probs_base || k->greedy_base || k->probs_ko || k->logp_ko || k->greedy_ko || k->kl || k->dlogp;
+    if (a->which != 0) any = any || a->values || k->values_ko || k->dvalue;
+    if (!any) return fail(IPLAN_EINVAL, "iplan_ac_knockout: no output of the selected nets was asked for");
+    return ac_knockout_launch(*k, (hipStream_t)stream);
 }

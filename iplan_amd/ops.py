@@ -769,22 +769,13 @@ def saliency(actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor=Non
     return res
 
 
-def saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
-                  avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, want=("y", "entity"), packed=None,
-                  out=None):
-    """The descriptor of a ``saliency`` launch, its output tensors and the operands to keep alive until the launch has been queued,
-    checked but not launched: (IplanAcSaliencyArgs, dict, tuple)."""
-    want = tuple(want)
-    assert want and all(k in SALIENCY_OUTPUTS for k in want), want
+def _saliency_rows(a, actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor, h_critic, h_strides, avail, avail_strides, target,
+                   target_strides, target_all, n_actions):
+    """What the launches over E x S rows with a GIVEN GRU state per row enter into their IplanAcSaliencyArgs ``a`` beside ``_ac_rows``:
+    the states, the nets, avail and the target, each checked to lie inside its storage -> the device"""
     M = L.AC_HIDDEN
-    a = L.AcSaliencyArgs()
     dev, _ = _ac_rows(a, actor_arena, critic_arena, which, spec, E, S, n_agents)
     a.target_all = target_all
-    n_src = sum(1 for s in spec.sources if s[1] > 0)
-    res = {}
-
-    def dest(k, shape, dtype=torch.float32):
-        return _dest(out, res, k, shape, dtype, dev)
 
     def reach(strides, width):
         assert len(strides) == 3 and min(strides) >= 0, strides
@@ -796,13 +787,6 @@ def saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_acto
         assert h is not None and h.dtype == torch.float32 and h.device == dev, ("the GRU state of the " + key + "s is needed",)
         _inside(h, reach(h_strides, M), "h_" + key)
         setattr(a, "h_" + key, h.data_ptr())
-        if "entity" in want:
-            setattr(a, "entity_" + key, dest("entity_" + key, (n_agents, E, S, spec.N, n_src, 2)))
-        if "input_grad" in want:
-            setattr(a, "input_grad_" + key, dest("input_grad_" + key, (n_agents, E, S, spec.F)))
-        if "act" in want:
-            setattr(a, "act1_" + key, dest("act1_" + key, (n_agents, E, S, M)))
-            setattr(a, "act2_" + key, dest("act2_" + key, (n_agents, E, S, M)))
     a.hs_net, a.hs_chain, a.hs_step = h_strides
     if which != 1:
         _fill_acnet(a.actor, actor_arena, L.ACTOR_PARAM_ORDER, n_actions)
@@ -816,15 +800,157 @@ def saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_acto
             _inside(target, reach(target_strides, 1), "target")
             a.target = target.data_ptr()
             a.tg_s_net, a.tg_s_chain, a.tg_s_step = target_strides
-        if "y" in want:
-            a.logp = dest("logp", (n_agents, E, S))
-            a.target_out = dest("target_action", (n_agents, E, S), torch.int64)
     if which != 0:
         _fill_acnet(a.critic, critic_arena, L.CRITIC_PARAM_ORDER, 1)
-        if "y" in want:
-            a.values = dest("values", (n_agents, E, S))
+    return dev
+
+
+def _saliency_y(a, which, dest, n_agents, E, S):
+    """logp, target_action and values [nA, E, S] of the selected nets as destinations of ``a``"""
+    if which != 1:
+        a.logp = dest("logp", (n_agents, E, S))
+        a.target_out = dest("target_action", (n_agents, E, S), torch.int64)
+    if which != 0:
+        a.values = dest("values", (n_agents, E, S))
+
+
+def saliency_args(actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
+                  avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, want=("y", "entity"), packed=None,
+                  out=None):
+    """The descriptor of a ``saliency`` launch, its output tensors and the operands to keep alive until the launch has been queued,
+    checked but not launched: (IplanAcSaliencyArgs, dict, tuple)."""
+    want = tuple(want)
+    assert want and all(k in SALIENCY_OUTPUTS for k in want), want
+    M = L.AC_HIDDEN
+    a = L.AcSaliencyArgs()
+    dev = _saliency_rows(a, actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor, h_critic, h_strides, avail, avail_strides, target,
+                         target_strides, target_all, n_actions)
+    n_src = sum(1 for s in spec.sources if s[1] > 0)
+    res = {}
+
+    def dest(k, shape, dtype=torch.float32):
+        return _dest(out, res, k, shape, dtype, dev)
+
+    for net, key in ((0, "actor"), (1, "critic")):
+        if which == 1 - net:
+            continue
+        if "entity" in want:
+            setattr(a, "entity_" + key, dest("entity_" + key, (n_agents, E, S, spec.N, n_src, 2)))
+        if "input_grad" in want:
+            setattr(a, "input_grad_" + key, dest("input_grad_" + key, (n_agents, E, S, spec.F)))
+        if "act" in want:
+            setattr(a, "act1_" + key, dest("act1_" + key, (n_agents, E, S, M)))
+            setattr(a, "act2_" + key, dest("act2_" + key, (n_agents, E, S, M)))
+    if "y" in want:
+        _saliency_y(a, which, dest, n_agents, E, S)
     _ac_packed(a, which, packed)
     return a, res, (spec, h_actor, h_critic, avail, target, packed)
+
+
+POLICY_KNOCKOUT_OUTPUTS = ("base", "kl", "dlogp", "dvalue", "greedy_ko", "probs_ko", "logp_ko", "values_ko")
+POLICY_KNOCKOUT_JOBS_PER_TILE = 15       # KO_JOBS of csrc/policy_knockout.hip: column 15 of every tile carries the row's base result
+
+
+def policy_knockout(actor_arena, critic_arena, which, spec, E, S, n_agents, jobs, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
+                    avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, knock=None, baseline=None,
+                    override=None, want=("kl",), packed=None, out=None, lib=None):
+    """R_Actor (which=0) / R_Critic (1) / both (2) of every agent on E x S recorded rows, run once per job with one entity's columns of
+    the selected sources replaced as the features are gathered (iplan_ac_knockout; include/iplan_hip.h: IplanAcKnockoutArgs), forward
+    only, the row's GRU state given and held.  ``spec``, h_*, avail, target, ``packed`` and their strides as for ``saliency``.
+    ``jobs``: J entity indices in [0, N), or -1 for "nothing knocked" (duplicates allowed), shared by all rows.  Per source, in the
+    order of ``spec.sources``: ``knock`` flags (None: every source), ``baseline`` rows [w] or None (zeros), ``override`` views
+    [nA, E, S, J, N, w] or None -- any non-negative strides with the innermost axis contiguous, read in place; an overridden source is
+    taken as given and not knocked as well.  ``want``: "base" (logp, values, target_action, greedy [nA,E,S] and probs [nA,E,S,n_actions]
+    of the rows with nothing knocked) and, [nA,E,S,J] each, kl = KL(pi_base || pi_ko), dlogp, dvalue, greedy_ko (int64), logp_ko,
+    values_ko, probs_ko [.., n_actions]; those the selected nets do not provide are left out.  ``out``: optional dict of contiguous
+    destinations.  Everything the kernel will read is bounds-checked here, on the host.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res, _keep = policy_knockout_args(actor_arena, critic_arena, which, spec, E, S, n_agents, jobs, h_actor, h_critic, h_strides, avail,
+                                         avail_strides, target, target_strides, target_all, n_actions, knock, baseline, override, want, packed, out)
+    dev = (actor_arena if which != 1 else critic_arena).data.device
+    nets = n_agents * (2 if which == 2 else 1)
+    cols = 16 * ((a.J + POLICY_KNOCKOUT_JOBS_PER_TILE - 1) // POLICY_KNOCKOUT_JOBS_PER_TILE)
+    _launch("ac_knockout", lambda: lib.call("iplan_ac_knockout", a, L.current_stream(dev)),
+            work=2.0 * nets * E * S * cols * L.AC_HIDDEN * (spec.F + 8 * L.AC_HIDDEN))
+    return res
+
+
+def policy_knockout_args(actor_arena, critic_arena, which, spec, E, S, n_agents, jobs, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
+                         avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, knock=None, baseline=None,
+                         override=None, want=("kl",), packed=None, out=None):
+    """The descriptor of a ``policy_knockout`` launch, its output tensors and the operands to keep alive until the launch has been
+    queued, checked but not launched: (IplanAcKnockoutArgs, dict, tuple)."""
+    want = tuple(want)
+    assert want and all(k in POLICY_KNOCKOUT_OUTPUTS for k in want), want
+    jobs = [int(j) for j in jobs]
+    J, N = len(jobs), spec.N
+    assert J >= 1 and all(-1 <= j < N for j in jobs), (jobs, N)
+    n_src = len(spec.sources)
+    # the rows, the states, avail and target as saliency describes them; its "y" outputs receive the base result
+    a = L.AcKnockoutArgs()
+    dev = _saliency_rows(a.base, actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor, h_critic, h_strides, avail, avail_strides, target,
+                         target_strides, target_all, n_actions)
+    _ac_packed(a.base, which, packed)
+    res = {}
+    keep = (spec, h_actor, h_critic, avail, target, packed)
+
+    def dest(k, shape, dtype=torch.float32):
+        return _dest(out, res, k, shape, dtype, dev)
+
+    if "base" in want:
+        _saliency_y(a.base, which, dest, n_agents, E, S)
+    a.J = J
+    j_host = (C.c_int32 * J)(*jobs)
+    j_dev = torch.tensor(jobs, dtype=torch.int32, device=dev)
+    a.jobs, a.jobs_host = j_dev.data_ptr(), C.cast(j_host, C.c_void_p)
+    keep = keep + (j_host, j_dev)
+
+    def per_source(seq, what):
+        seq = (None,) * n_src if seq is None else tuple(seq)
+        assert all(v is None or v is False for v in seq[n_src:]), (what, "names a source the rows do not have", n_src)
+        return seq[:n_src] + (None,) * (n_src - len(seq))
+
+    knock = (True,) * n_src if knock is None else per_source(knock, "knock")
+    baseline, override = per_source(baseline, "baseline"), per_source(override, "override")
+    for k, (_, w, _, _) in enumerate(spec.sources):
+        a.knock[k] = int(bool(knock[k]))
+        assert w > 0 or not (a.knock[k] or baseline[k] is not None or override[k] is not None), ("source", k, "is absent")
+        row = baseline[k]
+        if row is not None:
+            assert row.shape == (w,) and row.dtype == torch.float32 and row.is_contiguous() and row.device == dev, ("baseline", k, tuple(row.shape), w)
+            a.baseline[k] = row.data_ptr()
+        ov = override[k]
+        if ov is not None:
+            assert ov.shape == (n_agents, E, S, J, N, w) and ov.dtype == torch.float32 and ov.device == dev, ("override", k, tuple(ov.shape))
+            st = ov.stride()
+            assert min(st) >= 0 and (st[5] == 1 or w == 1), ("override", k, "negative stride or a strided innermost axis", st)
+            _inside(ov, sum((n - 1) * s for n, s in zip(ov.shape[:5], st[:5])) + w, "override")
+            a.override_src[k] = ov.data_ptr()
+            a.ov_s_net[k], a.ov_s_chain[k], a.ov_s_step[k], a.ov_s_job[k], a.ov_s_ent[k] = st[:5]
+        keep = keep + (row, ov)
+
+    pair = (n_agents, E, S, J)
+    if which != 1:
+        if "base" in want:
+            a.probs_base = dest("probs", (n_agents, E, S, n_actions))
+            a.greedy_base = dest("greedy", (n_agents, E, S), torch.int64)
+        if "kl" in want:
+            a.kl = dest("kl", pair)
+        if "dlogp" in want:
+            a.dlogp = dest("dlogp", pair)
+        if "greedy_ko" in want:
+            a.greedy_ko = dest("greedy_ko", pair, torch.int64)
+        if "probs_ko" in want:
+            a.probs_ko = dest("probs_ko", pair + (n_actions,))
+        if "logp_ko" in want:
+            a.logp_ko = dest("logp_ko", pair)
+    if which != 0:
+        if "dvalue" in want:
+            a.dvalue = dest("dvalue", pair)
+        if "values_ko" in want:
+            a.values_ko = dest("values_ko", pair)
+    assert res, ("nothing of", want, "is provided by the selected nets")
+    return a, res, keep
 
 
 def saliency_lag(actor_arena, critic_arena, which, spec, E, S, n_agents, lags, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
