@@ -1441,6 +1441,63 @@ typedef struct {
 
 int iplan_ac_knockout(const IplanAcKnockoutArgs* args, iplan_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Policy knock-out through time: E recorded chains are walked over H = base.S consecutive steps once per JOB, forward only, every job
+ * with a GRU state of its OWN, carried by the nets from the common start state base.hidden0_* (csrc/policy_knockout_trace.hip).  In
+ * steps 0 .. D-1 the job's entity has its columns of the knocked sources replaced AS THE FEATURES ARE GATHERED (jobs, knock, baseline:
+ * IplanAcKnockoutArgs' rules; no override); steps D .. H-1 see the recorded rows again, and only the job's state remembers the knock.
+ * `base` describes the chains exactly as for iplan_ac_trace: n_agents, E, S = H, which, act_tanh, feat (feat.T = H; the last action is
+ * teacher-forced from the batch for every job), the nets, hidden0_* and strides, avail, packed_*.  base.actions_in is the TARGET a*
+ * of step (e, s) by physical row; NULL, or an entry outside [0, n_actions): the BASE chain's argmax of that step -- one action per
+ * step, the same for every job.  Of base's outputs probs, greedy, logp (of a*) and values [n_agents, E, H, ..] receive the base chain
+ * (nothing knocked), which equals iplan_ac_trace's bits; entropy, h_all_* and h_last_* must be NULL.
+ *   phase 1 (knocked trunk)  steps < D only; one wave per tile of 16 columns = the jobs 15*jt .. 15*jt + 14 of ONE row and, in column 15,
+ *                    the row with nothing knocked; iplan_ac_trace's trunk arithmetic (the same k-tile order and partial sums of 8
+ *                    k-tiles) -> gi_ko, a caller-provided workspace [2 (actor | critic), n_agents, E, D, ceil(J/15), 16, IPLAN_AC_TRACE_GI]
+ *   phase 2 (knocked walk)   one workgroup per (net, chain, job tile) steps s = 0 .. H-1 with W_hh in registers; a column reads its own
+ *                    gi_ko row while s < D and base.gi of the row after: base.gi [2, n_agents, E*H, IPLAN_AC_TRACE_GI] as a call of
+ *                    iplan_ac_trace with phases = 1 on the same rows leaves it (needed when D < H; this entry does not write it).
+ * base.phases: 0 = both kernels, 1 = phase 1 only, 2 = phase 2 only (gi_ko as a previous call left it).
+ * Outputs, each optional, contiguous, of the nets base.which selects, slot (net, e, s, job) at index ((net*E + e)*H + s)*J + job:
+ *   probs_ko [.., n_actions]   logp_ko (of a*), values_ko, greedy_ko (int64, lowest index on ties)
+ *   logp_all_ko [.., n_actions]  every log-probability of the job's distribution, the operands of kl (for tests)
+ *   kl, dlogp, dvalue          as iplan_ac_knockout forms them, against the base chain's result of the same step
+ *   shift_sq_actor / _critic   sum over the 64 units, ascending, of (h_job - h_base)^2 after the step; every difference, product and sum
+ *                              rounded on its own (no fma)
+ *   h_ko_actor / h_ko_critic   [.., 64] the job's state after the step
+ *   target_out [n_agents, E, H] int64   the a* that was used
+ * A job whose gathered values equal the rows' own has kl = dlogp = dvalue = shift_sq = 0.0 at every step.  No atomics, no sums across
+ * columns: a slot's bits do not depend on its lane, tile, the other jobs, J, H (a shorter H gives a prefix), packed or in-place fc1 or
+ * the outputs asked for.  Refused: what iplan_ac_trace refuses of the chains, D outside [1, H], J < 1, a job outside [-1, N) (checked
+ * on jobs_host), knock or baseline on an absent source, E*H*ceil(J/15) tiles beyond 2^31 / 16, a base output other than probs / greedy
+ * / logp / values, no output (unless phases = 1), a missing gi_ko, a missing base.gi with D < H; gi_ko, base.gi, h_ko_* and the packed
+ * operands 16-byte aligned.
+ */
+typedef struct {
+    IplanAcTraceArgs base;
+    int32_t D, J;
+    int32_t knock[3];
+    const int32_t* jobs;        /* [J] device memory                                                       */
+    const int32_t* jobs_host;   /* the same values in host memory (argument checks)                        */
+    const float* baseline[3];   /* [w[k]] or NULL (zeros)                                                  */
+    float* gi_ko;
+    int64_t* target_out;
+    float* probs_ko;
+    float* logp_ko;
+    float* values_ko;
+    int64_t* greedy_ko;
+    float* kl;
+    float* dlogp;
+    float* dvalue;
+    float* shift_sq_actor;
+    float* shift_sq_critic;
+    float* h_ko_actor;
+    float* h_ko_critic;
+    float* logp_all_ko;
+} IplanAcKnockoutTraceArgs;
+
+int iplan_ac_knockout_trace(const IplanAcKnockoutTraceArgs* args, iplan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,7 +54,7 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_ac_xhat_pack", "iplan_ac_fc1_split_fwd", "iplan_ac_bwd_fc1_split",
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
                 "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
-                "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout"]
+                "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout", "iplan_ac_knockout_trace"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -536,6 +536,15 @@ class AcKnockoutArgs(C.Structure):
     ]
 
 
+class AcKnockoutTraceArgs(C.Structure):
+    _fields_ = [
+        ("base", AcTraceArgs), ("D", i32), ("J", i32), ("knock", i32 * 3), ("jobs", fp), ("jobs_host", fp), ("baseline", fp * 3),
+        ("gi_ko", fp), ("target_out", fp), ("probs_ko", fp), ("logp_ko", fp), ("values_ko", fp), ("greedy_ko", fp),
+        ("kl", fp), ("dlogp", fp), ("dvalue", fp), ("shift_sq_actor", fp), ("shift_sq_critic", fp), ("h_ko_actor", fp), ("h_ko_critic", fp),
+        ("logp_all_ko", fp),
+    ]
+
+
 # ---- FC behaviour ablation -------------------------------------------------------------------------------
 class Mlp3Args(C.Structure):
     _fields_ = [
@@ -576,4 +585,4 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanAcSaliencyArgs": AcSaliencyArgs, "IplanAcSaliencyLagArgs": AcSaliencyLagArgs,
                   "IplanEncSaliencyArgs": EncSaliencyArgs, "IplanGatSaliencyArgs": GatSaliencyArgs,
                   "IplanPdecSaliencyArgs": PdecSaliencyArgs, "IplanGatKnockoutArgs": GatKnockoutArgs,
-                  "IplanAcKnockoutArgs": AcKnockoutArgs}
+                  "IplanAcKnockoutArgs": AcKnockoutArgs, "IplanAcKnockoutTraceArgs": AcKnockoutTraceArgs}

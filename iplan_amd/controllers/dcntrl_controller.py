@@ -475,7 +475,7 @@ class DcntrlMAC:
         and dvalue are exactly 0.  Unavailable actions have probability exactly 0 and contribute nothing to kl; a row with no
         available action is uniform (``policy_trace``'s convention) and has kl = 0.  Device tensors in -> device tensors out, numpy in
         -> numpy out.  Draws from no generator; parameters, gradient entries, optimiser state, ``hidden_states`` and the batch are not
-        touched.  Not covered: layer_N / recurrent_N other than 1, knocking the GRU state, effects carried through time."""
+        touched.  Not covered: layer_N / recurrent_N other than 1, knocking the GRU state; effects carried through time are ``knockout_trace``'s."""
         a = self.args
         if a.layer_N != 1 or a.recurrent_N != 1:
             raise NotImplementedError("knockout covers layer_N = recurrent_N = 1 only")
@@ -603,6 +603,192 @@ class DcntrlMAC:
         if one:
             keep = meta + ("entity_kl", "entity_abs_dvalue", "flip_rate")
             out = {k: (v if k in keep else v[:, 0]) for k, v in out.items()}
+        return {k: (v if k in meta else v.cpu().numpy()) for k, v in out.items()} if as_np else out
+
+    KNOCKOUT_TRACE_WANT = ("kl", "probs_ko", "logp_ko", "values_ko", "h_actor_ko", "h_critic_ko", "summary")
+
+    def knockout_trace(self, batch, entities=None, start=0, duration=1, horizon=None, sources=None, baseline=None, target="recorded",
+                       which="both", hidden0=None, want=("kl",), presence_col=0, max_workspace_mb=256):
+        """How long does the policy remember a vehicle?  Vehicle j is hidden from the agents for ``duration`` = D steps from step
+        ``start`` and then shown again; the nets walk steps start .. start + H - 1 (``horizon`` = H, None: up to the batch's last
+        step; ``duration`` None: knocked throughout, D = H) once per entity j of ``entities`` and once with nothing knocked, every
+        chain with ITS OWN GRU state carried by the nets from a common start state (ops.policy_knockout_trace) -- what ``knockout``,
+        whose state is given and held, leaves out.  In job j the inputs of steps start .. start + D - 1 have j's columns of the selected
+        ``sources`` replaced as the kernel gathers the features (never the one-hots; the batch is read in place and not copied); steps
+        start + D .. see the recorded inputs again, and the only trace of the knock there is the job's own state: the echo.
+        ``batch``, ``entities`` (-1 = nothing knocked), ``sources``, ``baseline``, ``target``, ``which``, ``presence_col`` and
+        ``max_workspace_mb`` as for ``knockout``; ``hidden0`` as for ``policy_trace``, taken at ``start``: None = the batch's
+        ``rnn_states_*[:, start]``, "zeros", or a pair of [E, nA, M] tensors.  The last action is the recorded one, teacher-forced as in
+        ``policy_trace``: the counterfactual does not re-decide past actions.  With ``target="greedy"`` a* is the BASE chain's argmax
+        at that step, the same action for every job.
+        Returns a dict; pair axes [E, H, nA, J]:
+          kl = KL(pi_base || pi_ko), dlogp = logp_ko - logp_base (of a*), dvalue = V_ko - V_base, greedy (int64, lowest index on
+          ties), flip = greedy != the base chain's greedy -- each against the base chain at the same step;
+          state_shift_actor, state_shift_critic: the L2 distance of the job's GRU state from the base chain's after that step (the
+          kernel's fp32 sum of squares in unit order, torch's sqrt);
+          the base chain's logp, values, target_action, greedy_base [E, H, nA] and probs [E, H, nA, n_actions] (``policy_trace``'s bits);
+          knocked (the entity list), sources (the names that were knocked), window = (start, D, H);
+          probs_ko [.., n_actions], logp_ko, values_ko, h_actor_ko / h_critic_ko [.., M] (the job's state after every step) with those
+          names in ``want``;
+          echo_kl, echo_abs_dvalue, echo_flip_rate, echo_state_shift (of the actors; of the critics with which="critic") [nA, H, J]
+          float64 with "summary" in ``want``: means over the environments with weight ``batch["filled"][:, start + h]``, over the
+          pairs whose entity is present (``history[..., j, presence_col] != 0``) in at least one knocked step; every pair for job -1
+          and for ``presence_col`` < 0; 0 where no such pair exists; formed on the device in float64, in environment order.
+        ``want`` only ADDS results.  Those of a net ``which`` leaves out are missing.  Environments and jobs are chunked so that one
+        launch's outputs and its per-step gate workspaces stay below ``max_workspace_mb``; chunked and unchunked calls give the same
+        bits, and so do a shorter ``horizon`` (a prefix), packed or in-place fc1 and any ``want``.  A job whose replaced values equal
+        the originals has kl = dlogp = dvalue = state_shift = 0.0 at every step.  Device tensors in -> device tensors out, numpy in ->
+        numpy out.  Draws from no generator; parameters, gradient entries, optimiser state, ``hidden_states`` and the batch are not
+        touched.  Not covered: a per-job ``override`` of a source (the chain from an ``attention_knockout`` through time, which does
+        not exist yet), re-deciding the teacher-forced last action, knocking the state itself, data-parallel aggregation, and
+        layer_N / recurrent_N other than 1."""
+        a = self.args
+        if a.layer_N != 1 or a.recurrent_N != 1:
+            raise NotImplementedError("knockout_trace covers layer_N = recurrent_N = 1 only")
+        want = tuple(want)
+        if any(k not in self.KNOCKOUT_TRACE_WANT for k in want):
+            raise ValueError(f"knockout_trace: want={want!r} names something other than {self.KNOCKOUT_TRACE_WANT}")
+        if which not in ("actor", "critic", "both"):
+            raise ValueError(f"knockout_trace: which={which!r}")
+        if isinstance(target, str) and target not in ("recorded", "greedy"):
+            raise ValueError(f"knockout_trace: target={target!r}")
+        nA, M, N = self.n_agents, a.rnn_hidden_dim, a.max_vehicle_num
+        widths = self._widths()
+        names = [k for k, _ in widths]
+        ents = list(range(N)) if entities is None else [int(j) for j in np.asarray(entities).reshape(-1)]
+        if not ents or any(not -1 <= j < N for j in ents):
+            raise ValueError(f"knockout_trace: entities={ents!r} must be a non-empty list of indices in [-1, {N})")
+        srcs = tuple(names) if sources is None else tuple(sources)
+        if not srcs or any(k not in names for k in srcs):
+            raise ValueError(f"knockout_trace: sources={srcs!r} is not a non-empty subset of {names!r}")
+        if baseline is not None and (not isinstance(baseline, dict) or any(k not in names for k in baseline)):
+            raise ValueError(f"knockout_trace: baseline is a dict whose keys are among {names!r}")
+        T1 = batch["history"].shape[1]
+        ints = (int, np.integer)
+        if not isinstance(start, ints) or not 0 <= start < T1:
+            raise ValueError(f"knockout_trace: start={start!r} outside [0, {T1})")
+        start = int(start)
+        H = T1 - start if horizon is None else horizon
+        if not isinstance(H, ints) or not 1 <= H or start + H > T1:
+            raise ValueError(f"knockout_trace: horizon={horizon!r} must satisfy 1 <= horizon and start + horizon <= {T1}")
+        H = int(H)
+        D = H if duration is None else duration
+        if not isinstance(D, ints) or not 1 <= D <= H:
+            raise ValueError(f"knockout_trace: duration={duration!r} outside [1, horizon={H}]")
+        D = int(D)
+        if not isinstance(presence_col, ints) or presence_col >= widths[0][1]:
+            raise ValueError(f"knockout_trace: presence_col={presence_col!r} outside the history width {widths[0][1]} (< 0: every pair counts)")
+        if not max_workspace_mb > 0:
+            raise ValueError("knockout_trace: max_workspace_mb must be positive")
+        r = self._rows(batch, start, H)
+        E, as_np, dev = r.E, r.as_np, r.dev
+        J = len(ents)
+        if isinstance(hidden0, str):
+            if hidden0 != "zeros":
+                raise ValueError(f"knockout_trace: hidden0={hidden0!r}")
+            ha = hc = None
+            hs = (0, 0)
+        else:
+            if hidden0 is None:
+                ha, hc = r.field("rnn_states_actors", th.float32)[:, start], r.field("rnn_states_critics", th.float32)[:, start]
+            else:
+                ha, hc = (dev(h, th.float32) for h in hidden0)
+            assert ha.shape == hc.shape == (E, nA, M), (ha.shape, hc.shape, (E, nA, M))
+            if ha.stride() != hc.stride() or ha.stride(2) != 1:
+                ha, hc = ha.contiguous(), hc.contiguous()
+            hs = (ha.stride(1), ha.stride(0))
+        if isinstance(target, str):
+            tgt = r.acts if target == "recorded" else None
+        else:
+            t_in = dev(target, th.int64)
+            assert t_in.shape == r.acts.shape, (t_in.shape, tuple(r.acts.shape))
+            full = th.full((E, T1, nA), -1, dtype=th.int64, device=self.device)    # (addressed by physical row, like the batch's fields)
+            full[:, r.sl] = t_in
+            tgt = full[:, r.sl]
+        base_rows = []
+        for k, wd in widths:
+            row = None if baseline is None or baseline.get(k) is None else dev(baseline[k], th.float32).contiguous()
+            if row is not None and row.shape != (wd,):
+                raise ValueError(f"knockout_trace: baseline[{k!r}] has shape {tuple(row.shape)}, the source's width is {wd}")
+            base_rows.append(row)
+        knock = tuple(k in srcs for k in names)
+        w = {"actor": 0, "critic": 1, "both": 2}[which]
+        extra = tuple(k for k in ("probs_ko", "logp_ko", "values_ko") if k in want)
+        want_h = tuple(k for k in ("h_actor_ko", "h_critic_ko") if k in want)
+        ask = ("kl", "dlogp", "dvalue", "greedy_ko", "shift_sq") + extra + (("h_ko",) if want_h else ())
+        # chunks: whole environments x a range of jobs; one launch's per-pair outputs and gate workspaces below the budget
+        GI = 4 * ops.L.AC_TRACE_GI
+        pair_bytes = nA * H * (4 * 5 + 8 + 4 * (("logp_ko" in extra) + ("values_ko" in extra) + a.n_actions * ("probs_ko" in extra)) + 8 * M * bool(want_h))
+        job_bytes = pair_bytes + 2 * nA * D * GI * 16 // 15 + 1
+        env_bytes = 2 * nA * H * GI
+        budget = int(max_workspace_mb * 2 ** 20)
+        Jc = max(1, min(J, (budget - env_bytes) // job_bytes))
+        if Jc < J and Jc > 15:
+            Jc -= Jc % 15                                                                      # whole tiles
+        Ec = max(1, min(E, budget // (env_bytes + job_bytes * Jc)))
+        whole = Ec == E and Jc == J
+        res = {}
+        for e0 in range(0, E, Ec):
+            es = slice(e0, min(E, e0 + Ec))
+            En = es.stop - es.start
+            spec = r.spec
+            if not whole:
+                spec = ops.AcFeatureSpec(spec.N, [(t[es], wd, sn, sr) for t, wd, sn, sr in spec.sources], n_actions=spec.n_actions,
+                                         last_action=None if spec.last_action is None else spec.last_action[es], la_strides=spec.la_strides,
+                                         n_id=spec.n_id, T=H, T_phys=spec.T_phys)
+            for j0 in range(0, J, Jc):
+                js = slice(j0, min(J, j0 + Jc))
+                part = ops.policy_knockout_trace(self.actor_arena, self.critic_arena, w, spec, En, H, D, nA, ents[js],
+                                                 hidden0_actor=None if ha is None else ha[es], hidden0_critic=None if hc is None else hc[es],
+                                                 h_strides=hs, avail=r.avail[es], avail_strides=(r.avail.stride(2), r.avail.stride(1)),
+                                                 target=None if tgt is None else tgt[es],
+                                                 target_strides=(0, 0) if tgt is None else (tgt.stride(2), tgt.stride(1)),
+                                                 n_actions=a.n_actions, knock=knock, baseline=base_rows,
+                                                 want=ask + (("base",) if j0 == 0 else ()), packed=r.packed)
+                if whole:
+                    res = part
+                    continue
+                for k, v in part.items():
+                    pairwise = v.dim() >= 4 and k != "probs"
+                    if k not in res:
+                        shape = list(v.shape)
+                        shape[1] = E
+                        if pairwise:
+                            shape[3] = J
+                        res[k] = th.empty(shape, dtype=v.dtype, device=v.device)
+                    if pairwise:
+                        res[k][:, es, :, js] = v
+                    else:
+                        res[k][:, es] = v
+        out = {"knocked": tuple(ents), "sources": srcs, "window": (start, D, H)}
+        meta = tuple(out)
+        rename = {"greedy_ko": "greedy", "greedy": "greedy_base", "shift_sq_actor": "state_shift_actor", "shift_sq_critic": "state_shift_critic",
+                  "h_ko_actor": "h_actor_ko", "h_ko_critic": "h_critic_ko"}
+        for k, v in res.items():
+            name = rename.get(k, k)
+            if name in ("h_actor_ko", "h_critic_ko") and name not in want:
+                continue
+            v = v.permute(1, 2, 0, *range(3, v.dim()))
+            out[name] = v.sqrt() if name.startswith("state_shift") else v
+        if "greedy" in out:
+            out["flip"] = out["greedy"] != out["greedy_base"].unsqueeze(-1)
+        if "summary" in want:
+            filled = dev(batch["filled"]).reshape(-1, T1)[:, r.sl].to(th.float64)                # [E, H]
+            hist = r.field("history", th.float32)[:, start:start + D]                             # [E, D, nA, N, d]
+            idx = th.as_tensor([max(j, 0) for j in ents], device=self.device)
+            pres = th.as_tensor([j < 0 or presence_col < 0 for j in ents], device=self.device).expand(hist.shape[0], nA, J)
+            if presence_col >= 0:
+                pres = pres | (hist[..., presence_col].index_select(3, idx) != 0).any(1)          # [E, nA, J]: present in a knocked step
+            wt = filled[:, :, None, None] * pres[:, None]                                         # [E, H, nA, J]
+            shift = out.get("state_shift_actor", out.get("state_shift_critic"))
+            cols = [(name, v) for name, v in (("echo_kl", out.get("kl")), ("echo_abs_dvalue", None if "dvalue" not in out else out["dvalue"].abs()),
+                                              ("echo_flip_rate", out.get("flip")), ("echo_state_shift", shift)) if v is not None]
+            per_env = th.stack([v.to(th.float64) * wt for _, v in cols] + [wt]).permute(0, 1, 3, 2, 4)   # [n + 1, E, nA, H, J]
+            tot = th.zeros(len(cols) + 1, nA, H, J, dtype=th.float64, device=self.device)
+            for e in range(E):                                                                    # environment order
+                tot += per_env[:, e]
+            for k, (name, _) in enumerate(cols):
+                out[name] = th.where(tot[-1] > 0, tot[k] / tot[-1].clamp_min(1e-300), th.zeros_like(tot[k]))
         return {k: (v if k in meta else v.cpu().numpy()) for k, v in out.items()} if as_np else out
 
     def get_value_ippo(self, agent_id, obs, rnn_states_critic):

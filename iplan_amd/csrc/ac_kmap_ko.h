@@ -1,5 +1,6 @@
 // The knocked form of kfeat (ac_kmap.h): one column of a knock-out tile gathers its row's features with one entity's entries of the
-// selected sources replaced, or with a whole source read from the column's own vector (policy_knockout.hip).
+// selected sources replaced, or with a whole source read from the column's own vector (policy_knockout.hip, policy_knockout_trace.hip);
+// and what a job column of such a tile forms against the base column, knock_kl.
 #pragma once
 #include "ac_kmap.h"
 
@@ -51,6 +52,29 @@ __device__ __forceinline__ f32x4 kfeat_ko(const KMap& k, const KTile& kt, const 
         else v[q] = as_global(p)[q];
     }
     return v;
+}
+
+constexpr int KO_JOBS = 15;                // jobs per tile; column 15 carries the base
+
+// KL(base || column) of this lane's column, summed in ascending action order: lane (n, gg) holds actions 4 gg .. 4 gg + 3 of column n.
+// offm: bit q set = action 4 g + q of this lane is unavailable (the same for every column: they share the row).
+__device__ __forceinline__ float knock_kl(const f32x4& pb, const f32x4& lp, int offm, int n, int n_out) {
+#pragma clang fp contract(off)
+    float kl = 0.f;
+#pragma unroll
+    for (int gg = 0; gg < 4; ++gg) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float p_b = __shfl(pb[q], 15 + 16 * gg), l_b = __shfl(lp[q], 15 + 16 * gg), l_k = __shfl(lp[q], n + 16 * gg);
+            const int om = __shfl(offm, n + 16 * gg);
+            if (4 * gg + q < n_out && !((om >> q) & 1)) {
+                const float d = l_b - l_k;
+                const float t = p_b * d;
+                kl = kl + t;
+            }
+        }
+    }
+    return kl;
 }
 
 }  // namespace iplan

@@ -28,29 +28,6 @@
 
 namespace iplan {
 
-constexpr int KO_JOBS = 15;                // jobs per tile; column 15 carries the base
-
-// KL(base || column) of this lane's column, summed in ascending action order: lane (n, gg) holds actions 4 gg .. 4 gg + 3 of column n.
-// offm: bit q set = action 4 g + q of this lane is unavailable (the same for every column: they share the row).
-__device__ __forceinline__ float knock_kl(const f32x4& pb, const f32x4& lp, int offm, int n, int n_out) {
-#pragma clang fp contract(off)
-    float kl = 0.f;
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float p_b = __shfl(pb[q], 15 + 16 * gg), l_b = __shfl(lp[q], 15 + 16 * gg), l_k = __shfl(lp[q], n + 16 * gg);
-            const int om = __shfl(offm, n + 16 * gg);
-            if (4 * gg + q < n_out && !((om >> q) & 1)) {
-                const float d = l_b - l_k;
-                const float t = p_b * d;
-                kl = kl + t;
-            }
-        }
-    }
-    return kl;
-}
-
 __global__ __launch_bounds__(64 * SAL_WAVES) void ac_knockout_kernel(IplanAcKnockoutArgs ka) {
     const IplanAcSaliencyArgs& a = ka.base;
     const int net = (int)blockIdx.y, which = a.which == 2 ? (int)blockIdx.z : a.which;

@@ -29,36 +29,14 @@
 // so a walk split into several calls, a chain moved to another lane or tile, and a tile with fewer chains give the same bits.
 // Packed and in-place fc1 operands hold the same values (zeros past a block's end in both) and feed the same instructions: the
 // normalisation is written with explicit fmaf so that no contraction choice can differ -- same bits either way.
-#include "api_util.h"
-#include "wave_tile.h"
-#include "gru_tile.h"
-#include "ac_kmap.h"
+#include "trace_body.h"
 
 namespace iplan {
 
-constexpr int PM = IPLAN_AC_HIDDEN;        // 64
-constexpr int PT = PM / 16;                // 4 tiles
-constexpr int PGI = IPLAN_AC_TRACE_GI;     // 192
-constexpr int TRUNK_WAVES = 4;             // row tiles per workgroup of phase 1
-constexpr int TRUNK_GROUP = 8;             // k-tiles per partial sum
-constexpr int WALK_WAVES = 5;              // four GRU waves and the head wave
-constexpr int HLD = PM + 8;                // LDS row stride of the state
-
-// MLPBase activation (utils/mappo_utils/mlp.py:10); `tanh` is uniform
-__device__ __forceinline__ f32x4 trace_act4(f32x4 v, bool tanh) {
-    f32x4 r;
-    for (int q = 0; q < 4; ++q) r[q] = tanh ? tanh_f(v[q]) : (v[q] > 0.0f ? v[q] : 0.0f);
-    return r;
-}
-
-__device__ __forceinline__ int trace_which(const IplanAcTraceArgs& a) { return a.which == 2 ? (int)blockIdx.z : a.which; }
-
 // ---- phase 1 -----------------------------------------------------------------------------------------------------------------------
-struct TrunkOps {                          // operands of one k-tile
-    KTile kt;
-    f32x4 x, gm, bt, wf[PT];
-};
-
+#define TRUNK_KTILE(T) ktile(km, T)
+#define TRUNK_FEAT(kt) kfeat(km, kt, src, valid, last, net)
+#define TRUNK_GI_ROW a.gi + (((int64_t)which * a.n_agents + net) * rows + (valid ? r : 0)) * PGI
 __global__ __launch_bounds__(64 * TRUNK_WAVES) void ac_trace_trunk_kernel(IplanAcTraceArgs a) {
     const int net = (int)blockIdx.y, which = trace_which(a);
     const IplanAcNet& nw = which ? a.critic : a.actor;
@@ -81,75 +59,13 @@ __global__ __launch_bounds__(64 * TRUNK_WAVES) void ac_trace_trunk_kernel(IplanA
     const KMap km = make_kmap(ft);
     const int F = km.NW + km.n_actions + km.n_id, KT = km.kt0[4];
 
-    // LayerNorm(F) statistics: mean, then the centred second moment
-    float sum = 0.f;
-    for (int T = 0; T < KT; ++T) {
-        const f32x4 x = kfeat(km, ktile(km, T), src, valid, last, net);
-        sum += (x[0] + x[1]) + (x[2] + x[3]);
-    }
-    const float mu = group_sum(sum) / (float)F;
-    float sq = 0.f;
-    for (int T = 0; T < KT; ++T) {
-        const KTile kt = ktile(km, T);
-        const f32x4 x = kfeat(km, kt, src, valid, last, net);
-        for (int q = 0; q < 4; ++q)
-            if (q < kt.nv) { const float d = x[q] - mu; sq = fmaf(d, d, sq); }
-    }
-    const float rstd = 1.0f / sqrtf(group_sum(sq) / (float)F + 1e-5f);
-
-    // fc1 over the row's K tiles; operands from the fragment-major pack (iplan_ac_pack_fc1) or from the arena in place
-    const float* __restrict__ pkw = which ? a.packed_critic : a.packed_actor;
-    if (pkw) pkw += (int64_t)net * a.packed_s_net;
-    const float* __restrict__ pkg = pkw ? pkw + (int64_t)KT * 1024 : nullptr;
-    const float* __restrict__ pkb = pkw ? pkg + (int64_t)KT * 16 : nullptr;
-    const float* fnw = P + nw.off[IPLAN_AC_FN_W];
-    const float* fnb = P + nw.off[IPLAN_AC_FN_B];
-    const float* W1 = P + nw.off[IPLAN_AC_FC1_W];
-    auto kload = [&](int T, TrunkOps& o) {
-        o.kt = ktile(km, T);
-        o.x = kfeat(km, o.kt, src, valid, last, net);
-        if (pkw) {
-            o.gm = *reinterpret_cast<const f32x4*>(pkg + T * 16 + 4 * g);
-            o.bt = *reinterpret_cast<const f32x4*>(pkb + T * 16 + 4 * g);
-            for (int oo = 0; oo < PT; ++oo) o.wf[oo] = *reinterpret_cast<const f32x4*>(pkw + ((int64_t)(T * PT + oo) * 64 + l) * 4);
-            return;
-        }
-        o.gm = kcols(o.kt, fnw);
-        o.bt = kcols(o.kt, fnb);
-        for (int oo = 0; oo < PT; ++oo) o.wf[oo] = kcols(o.kt, W1 + (int64_t)(16 * oo + n) * F);
-    };
-    f32x4 acc[PT], part[PT];
-    for (int o = 0; o < PT; ++o) { acc[o] = splat4(0.f); part[o] = splat4(0.f); }
-    TrunkOps cur, nxt;
-    kload(0, cur);
-    for (int T = 0; T < KT; ++T) {
-        if (T + 1 < KT) kload(T + 1, nxt);
-        f32x4 xn;
-        for (int q = 0; q < 4; ++q) xn[q] = (valid && q < cur.kt.nv) ? fmaf((cur.x[q] - mu) * rstd, cur.gm[q], cur.bt[q]) : 0.f;
-        for (int oo = 0; oo < PT; ++oo) part[oo] = mma_block(cur.wf[oo], xn, part[oo]);
-        if ((T + 1) % TRUNK_GROUP == 0 || T + 1 == KT)
-            for (int oo = 0; oo < PT; ++oo) { acc[oo] += part[oo]; part[oo] = splat4(0.f); }
-        cur = nxt;
-    }
-
-    // the two 64-wide layers and the input side of the GRU
-    const bool tanh = a.act_tanh != 0;
-    f32x4 f1[PT], f2[PT];
-    for (int t = 0; t < PT; ++t) f1[t] = trace_act4(acc[t] + bfrag_a(P + nw.off[IPLAN_AC_FC1_B], t), tanh);
-    layer_norm_tiles<PT>(f1, P + nw.off[IPLAN_AC_LN1_W], P + nw.off[IPLAN_AC_LN1_B], nullptr, nullptr);
-    for (int t = 0; t < PT; ++t)
-        f2[t] = trace_act4(dense_tile_ga<PT>(P + nw.off[IPLAN_AC_FC2_W], PM, PM, 16 * t, f1, bfrag_a(P + nw.off[IPLAN_AC_FC2_B], t)), tanh);
-    layer_norm_tiles<PT>(f2, P + nw.off[IPLAN_AC_LN2_W], P + nw.off[IPLAN_AC_LN2_B], nullptr, nullptr);
-    float* girow = a.gi + (((int64_t)which * a.n_agents + net) * rows + (valid ? r : 0)) * PGI;
-    for (int t = 0; t < 3 * PT; ++t)
-        vstore_a(girow, valid, t, dense_tile_ga<PT>(P + nw.off[IPLAN_AC_WIH], PM, 3 * PM, 16 * t, f2, bfrag_a(P + nw.off[IPLAN_AC_BIH], t)));
+#include "trace_trunk_impl.h"
 }
+#undef TRUNK_KTILE
+#undef TRUNK_FEAT
+#undef TRUNK_GI_ROW
 
 // ---- phase 2 -----------------------------------------------------------------------------------------------------------------------
-struct WalkShared {
-    __attribute__((aligned(16))) float h[2][16][HLD];
-};
-
 __global__ __launch_bounds__(64 * WALK_WAVES) void ac_trace_walk_kernel(IplanAcTraceArgs a) {
     __shared__ __attribute__((aligned(16))) WalkShared sh;
     const int net = (int)blockIdx.y, which = trace_which(a);

@@ -953,6 +953,142 @@ def policy_knockout_args(actor_arena, critic_arena, which, spec, E, S, n_agents,
     return a, res, keep
 
 
+POLICY_KNOCKOUT_TRACE_OUTPUTS = ("base", "kl", "dlogp", "dvalue", "greedy_ko", "shift_sq", "probs_ko", "logp_ko", "values_ko", "h_ko", "logp_all_ko",
+                                 "gi_ko")
+
+
+def policy_knockout_trace_gi_floats(which, n_agents, E, H, D, J):
+    """floats of the two gi workspaces of one ``policy_knockout_trace`` launch: the rows' base gi [2, nA, E * H, 192] (not needed when
+    D = H) and the knocked columns' gi_ko [2, nA, E, D, ceil(J / 15), 16, 192]"""
+    JT = (J + POLICY_KNOCKOUT_JOBS_PER_TILE - 1) // POLICY_KNOCKOUT_JOBS_PER_TILE
+    return 2 * n_agents * E * L.AC_TRACE_GI * ((H if D < H else 0) + D * JT * 16)
+
+
+def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_agents, jobs, hidden0_actor=None, hidden0_critic=None,
+                          h_strides=(0, 0), avail=None, avail_strides=(0, 0), target=None, target_strides=(0, 0), n_actions=5, knock=None,
+                          baseline=None, want=("kl",), packed=None, out=None, lib=None):
+    """R_Actor (which=0) / R_Critic (1) / both (2) of every agent walked over the H consecutive steps of E recorded chains once per job,
+    every job with its own GRU state from the common ``hidden0_*`` (iplan_ac_knockout_trace; include/iplan_hip.h:
+    IplanAcKnockoutTraceArgs), forward only.  In steps 0 .. D-1 the job's entity has its columns of the knocked sources replaced as the
+    features are gathered; steps D .. H-1 see the recorded rows.  ``spec`` (T = H), hidden0_*, avail, ``packed`` and their strides as for
+    ``policy_trace``; ``jobs``, ``knock`` and ``baseline`` as for ``policy_knockout``.  ``target``: int64 a* by physical row with
+    (s_net, s_row) strides, None (or an entry outside [0, n_actions)): the base chain's argmax of the step.  With D < H the rows' base gi
+    comes from ``iplan_ac_trace`` with phases = 1, launched here first.  ``want``: "base" (probs [nA,E,H,n_actions], greedy, logp, values,
+    target_action [nA,E,H] of the chain with nothing knocked) and, [nA,E,H,J] each, kl, dlogp, dvalue, greedy_ko (int64), logp_ko,
+    values_ko, probs_ko [.., n_actions], "shift_sq" (shift_sq_actor / shift_sq_critic: the squared L2 distance of the job's state from the
+    base chain's after the step), "h_ko" (h_ko_actor / h_ko_critic [.., 64]), "logp_all_ko" ([.., n_actions], the operands of kl; tests) and "gi_ko" (the knocked workspace [2, nA, E, D, ceil(J/15),
+    16, 192] as a result; tests); those the selected nets do not provide are left out.  ``out``: optional dict of contiguous destinations.
+    Everything the kernels will read is bounds-checked here, on the host.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    want = tuple(want)
+    assert want and all(k in POLICY_KNOCKOUT_TRACE_OUTPUTS for k in want), want
+    jobs = [int(j) for j in jobs]
+    J, N, M = len(jobs), spec.N, L.AC_HIDDEN
+    assert J >= 1 and all(-1 <= j < N for j in jobs), (jobs, N)
+    assert 1 <= D <= H, (D, H)
+    JT = (J + POLICY_KNOCKOUT_JOBS_PER_TILE - 1) // POLICY_KNOCKOUT_JOBS_PER_TILE
+    n_src = len(spec.sources)
+    a = L.AcKnockoutTraceArgs()
+    b = a.base
+    dev, last_row = _ac_rows(b, actor_arena, critic_arena, which, spec, E, H, n_agents)
+    nets = n_agents * (2 if which == 2 else 1)
+    stream = L.current_stream(dev)
+    keep = [spec, hidden0_actor, hidden0_critic, avail, target, packed]
+    if D < H:
+        # the rows' base gi, once per row: the plain trunk over all E x H rows (the D knocked rows' entries are not read)
+        ta, _, tkeep = policy_trace_args(actor_arena, critic_arena, which, spec, E, H, n_agents, n_actions=n_actions, want=(), packed=packed)
+        ta.phases = 1
+        _launch("ac_trace", lambda: lib.call("iplan_ac_trace", ta, stream), work=2.0 * nets * E * H * M * (spec.F + 5 * M))
+        b.gi = ta.gi
+        keep.append(tkeep)
+    res = {}
+
+    def dest(k, shape, dtype=torch.float32):
+        return _dest(out, res, k, shape, dtype, dev)
+
+    for net, h0, key in ((0, hidden0_actor, "actor"), (1, hidden0_critic, "critic")):
+        if which == 1 - net or h0 is None:
+            continue
+        assert h0.dtype == torch.float32 and h0.device == dev and min(h_strides) >= 0
+        _inside(h0, (n_agents - 1) * h_strides[0] + (E - 1) * h_strides[1] + M, "hidden0_" + key)
+        setattr(b, "hidden0_" + key, h0.data_ptr())
+    b.h0_s_net, b.h0_s_chain = h_strides
+    a.D, a.J = D, J
+    j_host = (C.c_int32 * J)(*jobs)
+    j_dev = torch.tensor(jobs, dtype=torch.int32, device=dev)
+    a.jobs, a.jobs_host = j_dev.data_ptr(), C.cast(j_host, C.c_void_p)
+    keep += [j_host, j_dev]
+    knock = (True,) * n_src if knock is None else tuple(knock)
+    baseline = (None,) * n_src if baseline is None else tuple(baseline)
+    assert len(knock) == n_src and len(baseline) == n_src, (knock, baseline, n_src)
+    for k, (_, w, _, _) in enumerate(spec.sources):
+        a.knock[k] = int(bool(knock[k]))
+        assert w > 0 or not (a.knock[k] or baseline[k] is not None), ("source", k, "is absent")
+        row = baseline[k]
+        if row is not None:
+            assert row.shape == (w,) and row.dtype == torch.float32 and row.is_contiguous() and row.device == dev, ("baseline", k, tuple(row.shape), w)
+            a.baseline[k] = row.data_ptr()
+            keep.append(row)
+    pair = (n_agents, E, H, J)
+    if which != 1:
+        _fill_acnet(b.actor, actor_arena, L.ACTOR_PARAM_ORDER, n_actions)
+        if avail is not None:
+            assert avail.dtype == torch.int32 and avail.device == dev and min(avail_strides) >= 0
+            _inside(avail, (n_agents - 1) * avail_strides[0] + last_row * avail_strides[1] + n_actions, "avail")
+            b.avail = avail.data_ptr()
+            b.av_s_net, b.av_s_row = avail_strides
+        if target is not None:
+            assert target.dtype == torch.int64 and target.device == dev and min(target_strides) >= 0
+            _inside(target, (n_agents - 1) * target_strides[0] + last_row * target_strides[1] + 1, "target")
+            b.actions_in = target.data_ptr()
+            b.act_s_net, b.act_s_row = target_strides
+        if "base" in want:
+            b.probs = dest("probs", (n_agents, E, H, n_actions))
+            b.greedy = dest("greedy", (n_agents, E, H), torch.int64)
+            b.logp = dest("logp", (n_agents, E, H))
+            a.target_out = dest("target_action", (n_agents, E, H), torch.int64)
+        if "kl" in want:
+            a.kl = dest("kl", pair)
+        if "dlogp" in want:
+            a.dlogp = dest("dlogp", pair)
+        if "greedy_ko" in want:
+            a.greedy_ko = dest("greedy_ko", pair, torch.int64)
+        if "probs_ko" in want:
+            a.probs_ko = dest("probs_ko", pair + (n_actions,))
+        if "logp_ko" in want:
+            a.logp_ko = dest("logp_ko", pair)
+        if "logp_all_ko" in want:
+            a.logp_all_ko = dest("logp_all_ko", pair + (n_actions,))
+        if "shift_sq" in want:
+            a.shift_sq_actor = dest("shift_sq_actor", pair)
+        if "h_ko" in want:
+            a.h_ko_actor = dest("h_ko_actor", pair + (M,))
+    if which != 0:
+        _fill_acnet(b.critic, critic_arena, L.CRITIC_PARAM_ORDER, 1)
+        if "base" in want:
+            b.values = dest("values", (n_agents, E, H))
+        if "dvalue" in want:
+            a.dvalue = dest("dvalue", pair)
+        if "values_ko" in want:
+            a.values_ko = dest("values_ko", pair)
+        if "shift_sq" in want:
+            a.shift_sq_critic = dest("shift_sq_critic", pair)
+        if "h_ko" in want:
+            a.h_ko_critic = dest("h_ko_critic", pair + (M,))
+    assert res, ("nothing of", want, "is provided by the selected nets")
+    _ac_packed(b, which, packed)
+    gi_shape = (2, n_agents, E, D, JT, 16, L.AC_TRACE_GI)
+    if "gi_ko" in want:
+        a.gi_ko = dest("gi_ko", gi_shape)
+    else:
+        gi_ko = workspace(dev, 2 * n_agents * E * D * JT * 16 * L.AC_TRACE_GI, "ac_knockout_trace")
+        a.gi_ko = gi_ko.data_ptr()
+        keep.append(gi_ko)
+    _launch("ac_knockout_trace", lambda: lib.call("iplan_ac_knockout_trace", a, stream),
+            work=2.0 * nets * E * JT * 16 * M * (D * (spec.F + 5 * M) + H * 4 * M))
+    return res
+
+
 def saliency_lag(actor_arena, critic_arena, which, spec, E, S, n_agents, lags, h_actor=None, h_critic=None, h_strides=(0, 0, 0), avail=None,
                  avail_strides=(0, 0, 0), target=None, target_strides=(0, 0, 0), target_all=-1, n_actions=5, want=("y", "entity"), packed=None,
                  out=None, lib=None):
