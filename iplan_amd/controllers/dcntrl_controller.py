@@ -438,6 +438,112 @@ class DcntrlMAC:
                     out[net + "_" + k] = res[k + "_" + net].permute(1, 2, 0, 3)
         return {k: (v if k == "sources" else v.cpu().numpy()) for k, v in out.items()} if as_np else out
 
+    # ---- what knockout() and knockout_trace() share; ``name`` is the method's, for the messages
+    def _knock_request(self, name, want, entities, sources, which, presence_col, max_workspace_mb, **dicts):
+        """the arguments both methods validate alike -> (want, the entity list, the knocked source names, ``_widths()``)"""
+        a = self.args
+        if a.layer_N != 1 or a.recurrent_N != 1:
+            raise NotImplementedError(f"{name} covers layer_N = recurrent_N = 1 only")
+        want, allowed = tuple(want), getattr(self, name.upper() + "_WANT")
+        if any(k not in allowed for k in want):
+            raise ValueError(f"{name}: want={want!r} names something other than {allowed}")
+        if which not in ("actor", "critic", "both"):
+            raise ValueError(f"{name}: which={which!r}")
+        N, widths = a.max_vehicle_num, self._widths()
+        names = [k for k, _ in widths]
+        ents = list(range(N)) if entities is None else [int(j) for j in np.asarray(entities).reshape(-1)]
+        if not ents or any(not -1 <= j < N for j in ents):
+            raise ValueError(f"{name}: entities={ents!r} must be a non-empty list of indices in [-1, {N})")
+        srcs = tuple(names) if sources is None else tuple(sources)
+        if not srcs or any(k not in names for k in srcs):
+            raise ValueError(f"{name}: sources={srcs!r} is not a non-empty subset of {names!r}")
+        for what, d in dicts.items():
+            if d is not None and (not isinstance(d, dict) or any(k not in names for k in d)):
+                raise ValueError(f"{name}: {what} is a dict whose keys are among {names!r}")
+        if not isinstance(presence_col, (int, np.integer)) or presence_col >= widths[0][1]:
+            raise ValueError(f"{name}: presence_col={presence_col!r} outside the history width {widths[0][1]} (< 0: everything counts)")
+        if not max_workspace_mb > 0:
+            raise ValueError(f"{name}: max_workspace_mb must be positive")
+        return want, ents, srcs, widths
+
+    def _knock_baseline(self, name, baseline, widths, dev):
+        """``baseline`` (None, or a dict source name -> row [w]) as one contiguous fp32 row or None per source"""
+        rows = []
+        for k, wd in widths:
+            row = None if baseline is None or baseline.get(k) is None else dev(baseline[k], th.float32).contiguous()
+            if row is not None and row.shape != (wd,):
+                raise ValueError(f"{name}: baseline[{k!r}] has shape {tuple(row.shape)}, the source's width is {wd}")
+            rows.append(row)
+        return rows
+
+    @staticmethod
+    def _knock_chunks(r, S, J, Ec, Jc, launch):
+        """``launch(spec, es, js, first)`` -> its dict of [nA, En, S, ..] results, once per chunk of Ec whole environments (``es``, with the
+        rows' ``spec`` cut to them) x Jc jobs (``js``; ``first``: the chunk that also asks for the base results), scattered into [nA,
+        E, S, ..] tensors -- the per-pair ones, which have a job axis behind S, also along it.  One chunk: its dict as it is."""
+        E, whole, res = r.E, Ec == r.E and Jc == J, {}
+        for e0 in range(0, E, Ec):
+            es = slice(e0, min(E, e0 + Ec))
+            spec = r.spec
+            if not whole:
+                spec = ops.AcFeatureSpec(spec.N, [(t[es], wd, sn, sr) for t, wd, sn, sr in spec.sources], n_actions=spec.n_actions,
+                                         last_action=None if spec.last_action is None else spec.last_action[es], la_strides=spec.la_strides,
+                                         n_id=spec.n_id, T=S, T_phys=spec.T_phys)
+            for j0 in range(0, J, Jc):
+                js = slice(j0, min(J, j0 + Jc))
+                part = launch(spec, es, js, j0 == 0)
+                if whole:
+                    return part
+                for k, v in part.items():
+                    pairwise = v.dim() >= 4 and k != "probs"
+                    if k not in res:
+                        shape = list(v.shape)
+                        shape[1] = E
+                        if pairwise:
+                            shape[3] = J
+                        res[k] = th.empty(shape, dtype=v.dtype, device=v.device)
+                    if pairwise:
+                        res[k][:, es, :, js] = v
+                    else:
+                        res[k][:, es] = v
+        return res
+
+    _KNOCK_RENAME = {"greedy_ko": "greedy", "greedy": "greedy_base", "shift_sq_actor": "state_shift_actor", "shift_sq_critic": "state_shift_critic",
+                     "h_ko_actor": "h_actor_ko", "h_ko_critic": "h_critic_ko"}
+
+    def _knock_results(self, out, res, want):
+        """the launches' [nA, E, S, ..] results under the methods' names, environments first, into ``out``; the states only if wanted, the
+        state shifts as distances; flip = a greedy action other than the base's"""
+        for k, v in res.items():
+            name = self._KNOCK_RENAME.get(k, k)
+            if name in ("h_actor_ko", "h_critic_ko") and name not in want:
+                continue
+            v = v.permute(1, 2, 0, *range(3, v.dim()))
+            out[name] = v.sqrt() if name.startswith("state_shift") else v
+        if "greedy" in out:
+            out["flip"] = out["greedy"] != out["greedy_base"].unsqueeze(-1)
+
+    def _knock_presence(self, hist, ents, presence_col):
+        """[E, S, nA, J] bool: the entity of job j is present in row (e, s, a) of ``hist`` [E, S, nA, N, d] (its ``presence_col`` != 0);
+        always for job -1 and for ``presence_col`` < 0"""
+        pres = th.as_tensor([j < 0 or presence_col < 0 for j in ents], device=self.device).expand(*hist.shape[:3], len(ents))
+        if presence_col >= 0:
+            idx = th.as_tensor([max(j, 0) for j in ents], device=self.device)
+            pres = pres | (hist[..., presence_col].index_select(3, idx) != 0)
+        return pres
+
+    def _knock_means(self, out, cols, wt, per_env):
+        """``out[name]`` = the mean of v with weight ``wt`` [E, S, nA, J] for every (name, v) of ``cols`` with a v, 0 where the weights
+        sum to 0: float64 on the device, ``per_env`` taking a [E, S, nA, J] product to what one environment adds ([E, ..]), the
+        environments added in their order"""
+        cols = [(name, v) for name, v in cols if v is not None]
+        parts = th.stack([per_env(v.to(th.float64) * wt) for _, v in cols] + [per_env(wt)])     # [n + 1, E, ..]: weighted sums | weights
+        tot = th.zeros(parts.shape[0], *parts.shape[2:], dtype=th.float64, device=self.device)
+        for e in range(parts.shape[1]):                                                           # environment order
+            tot += parts[:, e]
+        for k, (name, _) in enumerate(cols):
+            out[name] = th.where(tot[-1] > 0, tot[k] / tot[-1].clamp_min(1e-300), th.zeros_like(tot[k]))
+
     KNOCKOUT_WANT = ("kl", "probs_ko", "logp_ko", "values_ko", "summary")
 
     def knockout(self, batch, entities=None, sources=None, baseline=None, override=None, target="recorded", which="both", hidden=None,
@@ -477,25 +583,9 @@ class DcntrlMAC:
         -> numpy out.  Draws from no generator; parameters, gradient entries, optimiser state, ``hidden_states`` and the batch are not
         touched.  Not covered: layer_N / recurrent_N other than 1, knocking the GRU state; effects carried through time are ``knockout_trace``'s."""
         a = self.args
-        if a.layer_N != 1 or a.recurrent_N != 1:
-            raise NotImplementedError("knockout covers layer_N = recurrent_N = 1 only")
-        want = tuple(want)
-        if any(k not in self.KNOCKOUT_WANT for k in want):
-            raise ValueError(f"knockout: want={want!r} names something other than {self.KNOCKOUT_WANT}")
-        if which not in ("actor", "critic", "both"):
-            raise ValueError(f"knockout: which={which!r}")
+        want, ents, srcs, widths = self._knock_request("knockout", want, entities, sources, which, presence_col, max_workspace_mb,
+                                                       baseline=baseline, override=override)
         nA, M, N = self.n_agents, a.rnn_hidden_dim, a.max_vehicle_num
-        widths = self._widths()
-        names = [k for k, _ in widths]
-        ents = list(range(N)) if entities is None else [int(j) for j in np.asarray(entities).reshape(-1)]
-        if not ents or any(not -1 <= j < N for j in ents):
-            raise ValueError(f"knockout: entities={ents!r} must be a non-empty list of indices in [-1, {N})")
-        srcs = tuple(names) if sources is None else tuple(sources)
-        if not srcs or any(k not in names for k in srcs):
-            raise ValueError(f"knockout: sources={srcs!r} is not a non-empty subset of {names!r}")
-        for what, d in (("baseline", baseline), ("override", override)):
-            if d is not None and (not isinstance(d, dict) or any(k not in names for k in d)):
-                raise ValueError(f"knockout: {what} is a dict whose keys are among {names!r}")
         T1 = batch["history"].shape[1]
         one = isinstance(steps, (int, np.integer))
         if steps is None:
@@ -507,10 +597,6 @@ class DcntrlMAC:
             if stride != 1 or t1 - t0 < 1:
                 raise ValueError("knockout: steps is None, an int or a non-empty slice with step 1")
             S = t1 - t0
-        if not isinstance(presence_col, (int, np.integer)) or presence_col >= widths[0][1]:
-            raise ValueError(f"knockout: presence_col={presence_col!r} outside the history width {widths[0][1]} (< 0: every row counts)")
-        if not max_workspace_mb > 0:
-            raise ValueError("knockout: max_workspace_mb must be positive")
         r = self._rows(batch, t0, S)
         E, as_np, dev = r.E, r.as_np, r.dev
         J = len(ents)
@@ -523,12 +609,8 @@ class DcntrlMAC:
             ha, hc = ha.contiguous(), hc.contiguous()
         tgt, tgt_strides = self._target(r, target)
         w = {"actor": 0, "critic": 1, "both": 2}[which]
-        base_rows, over = [], []
+        base_rows, over = self._knock_baseline("knockout", baseline, widths, dev), []
         for k, wd in widths:
-            row = None if baseline is None or baseline.get(k) is None else dev(baseline[k], th.float32).contiguous()
-            if row is not None and row.shape != (wd,):
-                raise ValueError(f"knockout: baseline[{k!r}] has shape {tuple(row.shape)}, the source's width is {wd}")
-            base_rows.append(row)
             ov = None if override is None or override.get(k) is None else dev(override[k], th.float32)
             if ov is not None:
                 if ov.shape != (E, S, nA, J, N, wd):
@@ -536,7 +618,7 @@ class DcntrlMAC:
                 if min(ov.stride()) < 0 or (wd > 1 and ov.stride(5) != 1):
                     ov = ov.contiguous()
             over.append(ov)
-        knock = tuple(k in srcs for k in names)
+        knock = tuple(k in srcs for k, _ in widths)
         extra = tuple(k for k in ("probs_ko", "logp_ko", "values_ko") if k in want)
         ask = ("kl", "dlogp", "dvalue", "greedy_ko") + extra
         # chunks: whole environments x a range of jobs, one launch's per-pair outputs below the budget
@@ -544,62 +626,23 @@ class DcntrlMAC:
         budget = int(max_workspace_mb * 2 ** 20)
         Jc = max(1, min(J, budget // pair_bytes))
         Ec = max(1, min(E, budget // (pair_bytes * Jc)))
-        whole = Ec == E and Jc == J
-        res = {}
-        for e0 in range(0, E, Ec):
-            es = slice(e0, min(E, e0 + Ec))
-            En = es.stop - es.start
-            spec = r.spec
-            if not whole:
-                spec = ops.AcFeatureSpec(spec.N, [(t[es], wd, sn, sr) for t, wd, sn, sr in spec.sources], n_actions=spec.n_actions,
-                                         last_action=None if spec.last_action is None else spec.last_action[es], la_strides=spec.la_strides,
-                                         n_id=spec.n_id, T=S, T_phys=spec.T_phys)
-            for j0 in range(0, J, Jc):
-                js = slice(j0, min(J, j0 + Jc))
-                part = ops.policy_knockout(self.actor_arena, self.critic_arena, w, spec, En, S, nA, ents[js], h_actor=ha[es], h_critic=hc[es],
-                                           h_strides=_esn(ha), avail=r.avail[es], avail_strides=_esn(r.avail),
-                                           target=None if tgt is None else tgt[es], target_strides=tgt_strides, target_all=-1,
-                                           n_actions=a.n_actions, knock=knock, baseline=base_rows,
-                                           override=[None if ov is None else ov[es, :, :, js].permute(2, 0, 1, 3, 4, 5) for ov in over],
-                                           want=ask + (("base",) if j0 == 0 else ()), packed=r.packed)
-                if whole:
-                    res = part
-                    continue
-                for k, v in part.items():
-                    pairwise = k in ask
-                    if k not in res:
-                        shape = list(v.shape)
-                        shape[1] = E
-                        if pairwise:
-                            shape[3] = J
-                        res[k] = th.empty(shape, dtype=v.dtype, device=v.device)
-                    if pairwise:
-                        res[k][:, es, :, js] = v
-                    else:
-                        res[k][:, es] = v
+
+        def launch(spec, es, js, first):
+            return ops.policy_knockout(self.actor_arena, self.critic_arena, w, spec, es.stop - es.start, S, nA, ents[js], h_actor=ha[es],
+                                       h_critic=hc[es], h_strides=_esn(ha), avail=r.avail[es], avail_strides=_esn(r.avail),
+                                       target=None if tgt is None else tgt[es], target_strides=tgt_strides, target_all=-1,
+                                       n_actions=a.n_actions, knock=knock, baseline=base_rows,
+                                       override=[None if ov is None else ov[es, :, :, js].permute(2, 0, 1, 3, 4, 5) for ov in over],
+                                       want=ask + (("base",) if first else ()), packed=r.packed)
+
         out = {"knocked": tuple(ents), "sources": srcs}
         meta = tuple(out)
-        rename = {"greedy_ko": "greedy", "greedy": "greedy_base"}
-        for k, v in res.items():
-            out[rename.get(k, k)] = v.permute(1, 2, 0, *range(3, v.dim()))
-        if "greedy" in out:
-            out["flip"] = out["greedy"] != out["greedy_base"].unsqueeze(-1)
+        self._knock_results(out, self._knock_chunks(r, S, J, Ec, Jc, launch), want)
         if "summary" in want:
             filled = dev(batch["filled"]).reshape(-1, T1)[:, r.sl].to(th.float64)                # [E, S]
-            hist = r.field("history", th.float32)[:, r.sl]                                        # [E, S, nA, N, d]
-            idx = th.as_tensor([max(j, 0) for j in ents], device=self.device)
-            pres = th.as_tensor([j < 0 or presence_col < 0 for j in ents], device=self.device).expand(*hist.shape[:3], J)
-            if presence_col >= 0:
-                pres = pres | (hist[..., presence_col].index_select(3, idx) != 0)                 # [E, S, nA, J]
-            wt = filled[:, :, None, None] * pres                                                  # [E, S, nA, J]
-            cols = [(name, v) for name, v in (("entity_kl", out.get("kl")), ("entity_abs_dvalue", None if "dvalue" not in out else out["dvalue"].abs()),
-                                              ("flip_rate", out.get("flip"))) if v is not None]
-            per_env = th.stack([(v.to(th.float64) * wt).sum(1) for _, v in cols] + [wt.sum(1)])   # [n + 1, E, nA, J]
-            tot = th.zeros(len(cols) + 1, nA, J, dtype=th.float64, device=self.device)
-            for e in range(E):                                                                    # environment order
-                tot += per_env[:, e]
-            for k, (name, _) in enumerate(cols):
-                out[name] = th.where(tot[-1] > 0, tot[k] / tot[-1].clamp_min(1e-300), th.zeros_like(tot[k]))
+            pres = self._knock_presence(r.field("history", th.float32)[:, r.sl], ents, presence_col)
+            self._knock_means(out, (("entity_kl", out.get("kl")), ("entity_abs_dvalue", None if "dvalue" not in out else out["dvalue"].abs()),
+                                    ("flip_rate", out.get("flip"))), filled[:, :, None, None] * pres, lambda x: x.sum(1))      # -> [nA, J]
         if one:
             keep = meta + ("entity_kl", "entity_abs_dvalue", "flip_rate")
             out = {k: (v if k in keep else v[:, 0]) for k, v in out.items()}
@@ -643,26 +686,11 @@ class DcntrlMAC:
         not exist yet), re-deciding the teacher-forced last action, knocking the state itself, data-parallel aggregation, and
         layer_N / recurrent_N other than 1."""
         a = self.args
-        if a.layer_N != 1 or a.recurrent_N != 1:
-            raise NotImplementedError("knockout_trace covers layer_N = recurrent_N = 1 only")
-        want = tuple(want)
-        if any(k not in self.KNOCKOUT_TRACE_WANT for k in want):
-            raise ValueError(f"knockout_trace: want={want!r} names something other than {self.KNOCKOUT_TRACE_WANT}")
-        if which not in ("actor", "critic", "both"):
-            raise ValueError(f"knockout_trace: which={which!r}")
+        want, ents, srcs, widths = self._knock_request("knockout_trace", want, entities, sources, which, presence_col, max_workspace_mb,
+                                                       baseline=baseline)
         if isinstance(target, str) and target not in ("recorded", "greedy"):
             raise ValueError(f"knockout_trace: target={target!r}")
-        nA, M, N = self.n_agents, a.rnn_hidden_dim, a.max_vehicle_num
-        widths = self._widths()
-        names = [k for k, _ in widths]
-        ents = list(range(N)) if entities is None else [int(j) for j in np.asarray(entities).reshape(-1)]
-        if not ents or any(not -1 <= j < N for j in ents):
-            raise ValueError(f"knockout_trace: entities={ents!r} must be a non-empty list of indices in [-1, {N})")
-        srcs = tuple(names) if sources is None else tuple(sources)
-        if not srcs or any(k not in names for k in srcs):
-            raise ValueError(f"knockout_trace: sources={srcs!r} is not a non-empty subset of {names!r}")
-        if baseline is not None and (not isinstance(baseline, dict) or any(k not in names for k in baseline)):
-            raise ValueError(f"knockout_trace: baseline is a dict whose keys are among {names!r}")
+        nA, M = self.n_agents, a.rnn_hidden_dim
         T1 = batch["history"].shape[1]
         ints = (int, np.integer)
         if not isinstance(start, ints) or not 0 <= start < T1:
@@ -676,10 +704,6 @@ class DcntrlMAC:
         if not isinstance(D, ints) or not 1 <= D <= H:
             raise ValueError(f"knockout_trace: duration={duration!r} outside [1, horizon={H}]")
         D = int(D)
-        if not isinstance(presence_col, ints) or presence_col >= widths[0][1]:
-            raise ValueError(f"knockout_trace: presence_col={presence_col!r} outside the history width {widths[0][1]} (< 0: every pair counts)")
-        if not max_workspace_mb > 0:
-            raise ValueError("knockout_trace: max_workspace_mb must be positive")
         r = self._rows(batch, start, H)
         E, as_np, dev = r.E, r.as_np, r.dev
         J = len(ents)
@@ -705,13 +729,8 @@ class DcntrlMAC:
             full = th.full((E, T1, nA), -1, dtype=th.int64, device=self.device)    # (addressed by physical row, like the batch's fields)
             full[:, r.sl] = t_in
             tgt = full[:, r.sl]
-        base_rows = []
-        for k, wd in widths:
-            row = None if baseline is None or baseline.get(k) is None else dev(baseline[k], th.float32).contiguous()
-            if row is not None and row.shape != (wd,):
-                raise ValueError(f"knockout_trace: baseline[{k!r}] has shape {tuple(row.shape)}, the source's width is {wd}")
-            base_rows.append(row)
-        knock = tuple(k in srcs for k in names)
+        base_rows = self._knock_baseline("knockout_trace", baseline, widths, dev)
+        knock = tuple(k in srcs for k, _ in widths)
         w = {"actor": 0, "critic": 1, "both": 2}[which]
         extra = tuple(k for k in ("probs_ko", "logp_ko", "values_ko") if k in want)
         want_h = tuple(k for k in ("h_actor_ko", "h_critic_ko") if k in want)
@@ -726,69 +745,26 @@ class DcntrlMAC:
         if Jc < J and Jc > 15:
             Jc -= Jc % 15                                                                      # whole tiles
         Ec = max(1, min(E, budget // (env_bytes + job_bytes * Jc)))
-        whole = Ec == E and Jc == J
-        res = {}
-        for e0 in range(0, E, Ec):
-            es = slice(e0, min(E, e0 + Ec))
-            En = es.stop - es.start
-            spec = r.spec
-            if not whole:
-                spec = ops.AcFeatureSpec(spec.N, [(t[es], wd, sn, sr) for t, wd, sn, sr in spec.sources], n_actions=spec.n_actions,
-                                         last_action=None if spec.last_action is None else spec.last_action[es], la_strides=spec.la_strides,
-                                         n_id=spec.n_id, T=H, T_phys=spec.T_phys)
-            for j0 in range(0, J, Jc):
-                js = slice(j0, min(J, j0 + Jc))
-                part = ops.policy_knockout_trace(self.actor_arena, self.critic_arena, w, spec, En, H, D, nA, ents[js],
-                                                 hidden0_actor=None if ha is None else ha[es], hidden0_critic=None if hc is None else hc[es],
-                                                 h_strides=hs, avail=r.avail[es], avail_strides=(r.avail.stride(2), r.avail.stride(1)),
-                                                 target=None if tgt is None else tgt[es],
-                                                 target_strides=(0, 0) if tgt is None else (tgt.stride(2), tgt.stride(1)),
-                                                 n_actions=a.n_actions, knock=knock, baseline=base_rows,
-                                                 want=ask + (("base",) if j0 == 0 else ()), packed=r.packed)
-                if whole:
-                    res = part
-                    continue
-                for k, v in part.items():
-                    pairwise = v.dim() >= 4 and k != "probs"
-                    if k not in res:
-                        shape = list(v.shape)
-                        shape[1] = E
-                        if pairwise:
-                            shape[3] = J
-                        res[k] = th.empty(shape, dtype=v.dtype, device=v.device)
-                    if pairwise:
-                        res[k][:, es, :, js] = v
-                    else:
-                        res[k][:, es] = v
+
+        def launch(spec, es, js, first):
+            return ops.policy_knockout_trace(self.actor_arena, self.critic_arena, w, spec, es.stop - es.start, H, D, nA, ents[js],
+                                             hidden0_actor=None if ha is None else ha[es], hidden0_critic=None if hc is None else hc[es],
+                                             h_strides=hs, avail=r.avail[es], avail_strides=(r.avail.stride(2), r.avail.stride(1)),
+                                             target=None if tgt is None else tgt[es],
+                                             target_strides=(0, 0) if tgt is None else (tgt.stride(2), tgt.stride(1)),
+                                             n_actions=a.n_actions, knock=knock, baseline=base_rows,
+                                             want=ask + (("base",) if first else ()), packed=r.packed)
+
         out = {"knocked": tuple(ents), "sources": srcs, "window": (start, D, H)}
         meta = tuple(out)
-        rename = {"greedy_ko": "greedy", "greedy": "greedy_base", "shift_sq_actor": "state_shift_actor", "shift_sq_critic": "state_shift_critic",
-                  "h_ko_actor": "h_actor_ko", "h_ko_critic": "h_critic_ko"}
-        for k, v in res.items():
-            name = rename.get(k, k)
-            if name in ("h_actor_ko", "h_critic_ko") and name not in want:
-                continue
-            v = v.permute(1, 2, 0, *range(3, v.dim()))
-            out[name] = v.sqrt() if name.startswith("state_shift") else v
-        if "greedy" in out:
-            out["flip"] = out["greedy"] != out["greedy_base"].unsqueeze(-1)
+        self._knock_results(out, self._knock_chunks(r, H, J, Ec, Jc, launch), want)
         if "summary" in want:
             filled = dev(batch["filled"]).reshape(-1, T1)[:, r.sl].to(th.float64)                # [E, H]
-            hist = r.field("history", th.float32)[:, start:start + D]                             # [E, D, nA, N, d]
-            idx = th.as_tensor([max(j, 0) for j in ents], device=self.device)
-            pres = th.as_tensor([j < 0 or presence_col < 0 for j in ents], device=self.device).expand(hist.shape[0], nA, J)
-            if presence_col >= 0:
-                pres = pres | (hist[..., presence_col].index_select(3, idx) != 0).any(1)          # [E, nA, J]: present in a knocked step
-            wt = filled[:, :, None, None] * pres[:, None]                                         # [E, H, nA, J]
+            pres = self._knock_presence(r.field("history", th.float32)[:, start:start + D], ents, presence_col).any(1)   # in a knocked step
             shift = out.get("state_shift_actor", out.get("state_shift_critic"))
-            cols = [(name, v) for name, v in (("echo_kl", out.get("kl")), ("echo_abs_dvalue", None if "dvalue" not in out else out["dvalue"].abs()),
-                                              ("echo_flip_rate", out.get("flip")), ("echo_state_shift", shift)) if v is not None]
-            per_env = th.stack([v.to(th.float64) * wt for _, v in cols] + [wt]).permute(0, 1, 3, 2, 4)   # [n + 1, E, nA, H, J]
-            tot = th.zeros(len(cols) + 1, nA, H, J, dtype=th.float64, device=self.device)
-            for e in range(E):                                                                    # environment order
-                tot += per_env[:, e]
-            for k, (name, _) in enumerate(cols):
-                out[name] = th.where(tot[-1] > 0, tot[k] / tot[-1].clamp_min(1e-300), th.zeros_like(tot[k]))
+            self._knock_means(out, (("echo_kl", out.get("kl")), ("echo_abs_dvalue", None if "dvalue" not in out else out["dvalue"].abs()),
+                                    ("echo_flip_rate", out.get("flip")), ("echo_state_shift", shift)),
+                              filled[:, :, None, None] * pres[:, None], lambda x: x.permute(0, 2, 1, 3))                      # -> [nA, H, J]
         return {k: (v if k in meta else v.cpu().numpy()) for k, v in out.items()} if as_np else out
 
     def get_value_ippo(self, agent_id, obs, rnn_states_critic):

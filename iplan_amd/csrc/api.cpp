@@ -59,31 +59,58 @@ extern "C" int iplan_ppo_eval(const IplanPpoEvalArgs* a, iplan_stream_t stream) 
     return ppo_eval_launch(*a, (hipStream_t)stream);
 }
 
+__attribute__((visibility("hidden"))) int iplan::ac_rows_check(const char* who, const char* steps, const IplanAcFeatures& ft, int which, int n_agents, int S,
+                                                               const IplanAcNet& actor, const IplanAcNet& critic) {
+    if (which < 0 || which > 2 || n_agents < 1) return fail(IPLAN_EINVAL, "%s: bad which=%d / n_agents=%d", who, which, n_agents);
+    if (ft.N < 1 || ft.N > IPLAN_MAX_ENTITIES) return fail(IPLAN_EINVAL, "%s: N=%d outside [1,%d]", who, ft.N, IPLAN_MAX_ENTITIES);
+    if (ft.T != S || ft.T_phys < ft.T)
+        return fail(IPLAN_EINVAL, "%s: feat.T=%d must equal %s=%d and T_phys=%d must not be smaller", who, ft.T, steps, S, ft.T_phys);
+    if (ft.n_actions < 0 || ft.n_id < 0 || ft.w[0] < 0 || ft.w[1] < 0 || ft.w[2] < 0 || ft.N * (ft.w[0] + ft.w[1] + ft.w[2]) + ft.n_actions + ft.n_id < 1)
+        return fail(IPLAN_EINVAL, "%s: bad feature widths", who);
+    for (int s = 0; s < 3; ++s)
+        if (ft.w[s] > 0 && !ft.src[s]) return fail(IPLAN_EINVAL, "%s: feature source %d is null", who, s);
+    if (which != 1) {
+        if (actor.n_out < 1 || actor.n_out > 16) return fail(IPLAN_EINVAL, "%s: n_actions=%d outside [1,16]", who, actor.n_out);
+        if (!actor.params) return fail(IPLAN_EINVAL, "%s: actor parameters missing", who);
+    }
+    if (which != 0) {
+        if (critic.n_out != 1) return fail(IPLAN_EINVAL, "%s: the critic's head has one output (got %d)", who, critic.n_out);
+        if (!critic.params) return fail(IPLAN_EINVAL, "%s: critic parameters missing", who);
+    }
+    return IPLAN_OK;
+}
+
+__attribute__((visibility("hidden"))) int iplan::ac_jobs_check(const char* who, const char* steps, const IplanAcFeatures& ft, int E, int S, int J,
+                                                               const int32_t* jobs, const int32_t* jobs_host, const int32_t* knock,
+                                                               const float* const* baseline) {
+    if (J < 1) return fail(IPLAN_EINVAL, "%s: J=%d, at least one job is needed", who, J);
+    if (!jobs || !jobs_host) return fail(IPLAN_EINVAL, "%s: the job list is missing (device and host copy)", who);
+    for (int s = 0; s < J; ++s)
+        if (jobs_host[s] < -1 || jobs_host[s] >= ft.N) return fail(IPLAN_EINVAL, "%s: job %d = %d outside [-1,%d)", who, s, jobs_host[s], ft.N);
+    const int64_t tiles_per_row = (J + 14) / 15;
+    if ((int64_t)E * S * tiles_per_row > 0x7fffffff / 16)
+        return fail(IPLAN_EINVAL, "%s: E * %s * ceil(J / 15) = %lld tiles are too many", who, steps, (long long)E * S * tiles_per_row);
+    for (int s = 0; s < 3; ++s) {
+        if (knock[s] && ft.w[s] == 0) return fail(IPLAN_EINVAL, "%s: source %d is to be knocked, but it is absent", who, s);
+        if (baseline[s] && ft.w[s] == 0) return fail(IPLAN_EINVAL, "%s: a baseline for the absent source %d", who, s);
+    }
+    return IPLAN_OK;
+}
+
 // the checks iplan_ac_saliency and iplan_ac_saliency_lag share; `outputs`: at least one output must be asked for
 static int saliency_check(const IplanAcSaliencyArgs* a, bool outputs) {
     using namespace iplan;
-    if (a->which < 0 || a->which > 2 || a->n_agents < 1) return fail(IPLAN_EINVAL, "iplan_ac_saliency: bad which=%d / n_agents=%d", a->which, a->n_agents);
     if (a->E < 1 || a->S < 1) return fail(IPLAN_EINVAL, "iplan_ac_saliency: E=%d x S=%d rows, at least one row is needed", a->E, a->S);
     if ((int64_t)a->E * a->S > 0x7fffffff / 16) return fail(IPLAN_EINVAL, "iplan_ac_saliency: E * S = %lld rows are too many", (long long)a->E * a->S);
-    const IplanAcFeatures& ft = a->feat;
-    if (ft.N < 1 || ft.N > IPLAN_MAX_ENTITIES) return fail(IPLAN_EINVAL, "iplan_ac_saliency: N=%d outside [1,%d]", ft.N, IPLAN_MAX_ENTITIES);
-    if (ft.T != a->S || ft.T_phys < ft.T) return fail(IPLAN_EINVAL, "iplan_ac_saliency: feat.T=%d must equal S=%d and T_phys=%d must not be smaller", ft.T, a->S, ft.T_phys);
-    if (ft.n_actions < 0 || ft.n_id < 0 || ft.w[0] < 0 || ft.w[1] < 0 || ft.w[2] < 0 || ft.N * (ft.w[0] + ft.w[1] + ft.w[2]) + ft.n_actions + ft.n_id < 1)
-        return fail(IPLAN_EINVAL, "iplan_ac_saliency: bad feature widths");
-    for (int s = 0; s < 3; ++s)
-        if (ft.w[s] > 0 && !ft.src[s]) return fail(IPLAN_EINVAL, "iplan_ac_saliency: feature source %d is null", s);
+    if (const int rc = ac_rows_check("iplan_ac_saliency", "S", a->feat, a->which, a->n_agents, a->S, a->actor, a->critic)) return rc;
     bool any = false;
     if (a->which != 1) {
-        if (a->actor.n_out < 1 || a->actor.n_out > 16) return fail(IPLAN_EINVAL, "iplan_ac_saliency: n_actions=%d outside [1,16]", a->actor.n_out);
-        if (!a->actor.params) return fail(IPLAN_EINVAL, "iplan_ac_saliency: actor parameters missing");
         if (!a->h_actor) return fail(IPLAN_EINVAL, "iplan_ac_saliency: the actors' GRU state h_actor is missing");
         if (!a->target && (a->target_all < -1 || a->target_all >= a->actor.n_out))
             return fail(IPLAN_EINVAL, "iplan_ac_saliency: target action %d outside [-1,%d)", a->target_all, a->actor.n_out);
         any = any || a->logp || a->target_out || a->entity_actor || a->input_grad_actor || a->act1_actor || a->act2_actor;
     }
     if (a->which != 0) {
-        if (a->critic.n_out != 1) return fail(IPLAN_EINVAL, "iplan_ac_saliency: the critic's head has one output (got %d)", a->critic.n_out);
-        if (!a->critic.params) return fail(IPLAN_EINVAL, "iplan_ac_saliency: critic parameters missing");
         if (!a->h_critic) return fail(IPLAN_EINVAL, "iplan_ac_saliency: the critics' GRU state h_critic is missing");
         any = any || a->values || a->entity_critic || a->input_grad_critic || a->act1_critic || a->act2_critic;
     }
@@ -137,17 +164,8 @@ extern "C" int iplan_ac_knockout(const IplanAcKnockoutArgs* k, iplan_stream_t st
     if (a->entity_actor || a->entity_critic || a->input_grad_actor || a->input_grad_critic || a->act1_actor || a->act2_actor || a->act1_critic ||
         a->act2_critic)
         return fail(IPLAN_EINVAL, "iplan_ac_knockout: of base's outputs only logp, values and target_out (the base result) are written");
-    if (k->J < 1) return fail(IPLAN_EINVAL, "iplan_ac_knockout: J=%d, at least one job is needed", k->J);
-    if (!k->jobs || !k->jobs_host) return fail(IPLAN_EINVAL, "iplan_ac_knockout: the job list is missing (device and host copy)");
-    for (int s = 0; s < k->J; ++s)
-        if (k->jobs_host[s] < -1 || k->jobs_host[s] >= a->feat.N)
-            return fail(IPLAN_EINVAL, "iplan_ac_knockout: job %d = %d outside [-1,%d)", s, k->jobs_host[s], a->feat.N);
-    const int64_t tiles_per_row = (k->J + 14) / 15;
-    if ((int64_t)a->E * a->S * tiles_per_row > 0x7fffffff / 16)
-        return fail(IPLAN_EINVAL, "iplan_ac_knockout: E * S * ceil(J / 15) = %lld tiles are too many", (long long)a->E * a->S * tiles_per_row);
+    if (const int rc = ac_jobs_check("iplan_ac_knockout", "S", a->feat, a->E, a->S, k->J, k->jobs, k->jobs_host, k->knock, k->baseline)) return rc;
     for (int s = 0; s < 3; ++s) {
-        if (k->knock[s] && a->feat.w[s] == 0) return fail(IPLAN_EINVAL, "iplan_ac_knockout: source %d is to be knocked, but it is absent", s);
-        if (k->baseline[s] && a->feat.w[s] == 0) return fail(IPLAN_EINVAL, "iplan_ac_knockout: a baseline for the absent source %d", s);
         if (k->override_src[s] && a->feat.w[s] == 0) return fail(IPLAN_EINVAL, "iplan_ac_knockout: an override for the absent source %d", s);
         if (k->override_src[s] && (k->ov_s_job[s] < 0 || k->ov_s_net[s] < 0 || k->ov_s_chain[s] < 0 || k->ov_s_step[s] < 0 || k->ov_s_ent[s] < 0))
             return fail(IPLAN_EINVAL, "iplan_ac_knockout: negative override stride of source %d", s);

@@ -35,7 +35,7 @@ __device__ __forceinline__ int64_t ko_trace_tiles(const IplanAcKnockoutTraceArgs
 
 // ---- phase 1 -----------------------------------------------------------------------------------------------------------------------
 #define TRUNK_KTILE(T) sal_ktile(sm, T)
-#define TRUNK_FEAT(kt) feat(kt)
+#define TRUNK_FEAT(kt) knock_feat(km, sm, kt, col, net)
 #define TRUNK_GI_ROW ka.gi_ko + ((((((int64_t)which * a.n_agents + net) * a.E + ec) * D + sc) * JT + jt) * 16 + n) * PGI
 __global__ __launch_bounds__(64 * TRUNK_WAVES) void ac_knockout_trace_trunk_kernel(IplanAcKnockoutTraceArgs ka) {
     const IplanAcTraceArgs& a = ka.base;
@@ -44,42 +44,17 @@ __global__ __launch_bounds__(64 * TRUNK_WAVES) void ac_knockout_trace_trunk_kern
     const float* __restrict__ P = nw.params + (int64_t)net * nw.params_s_net;
     const IplanAcFeatures& ft = a.feat;
     const int l = lane_id(), w = uniform_i(wave_id()), n = l & 15, g = l >> 4;
-    const int D = ka.D, J = ka.J, JT = (int)ko_trace_tiles(ka);
+    const int D = ka.D, JT = (int)ko_trace_tiles(ka);
     const int64_t rows = (int64_t)a.E * D;                                   // the knocked rows
     const int64_t tile = (int64_t)blockIdx.x * TRUNK_WAVES + w;
     if (tile >= rows * JT) return;                                           // (whole wave; the kernel has no barrier)
-    const int64_t r = tile / JT;                                             // the recorded row all 16 columns share
-    const int jt = (int)(tile - r * JT);
-    const int slot = KO_JOBS * jt + n;                                       // this column's entry of jobs[]
-    const bool is_base = n == KO_JOBS;
-    const bool valid = is_base || slot < J;
-    const int64_t ec = r / D, sc = r % D;
-    const int64_t pr = ec * ft.T_phys + sc;
-    const float* const p0 = ft.w[0] > 0 ? ft.src[0] + (int64_t)net * ft.s_net[0] + pr * ft.s_row[0] : nullptr;
-    const float* const p1 = ft.w[1] > 0 ? ft.src[1] + (int64_t)net * ft.s_net[1] + pr * ft.s_row[1] : nullptr;
-    const float* const p2 = ft.w[2] > 0 ? ft.src[2] + (int64_t)net * ft.s_net[2] + pr * ft.s_row[2] : nullptr;
-    int last = -1;
-    if (ft.n_actions > 0) {
-        if (ft.last_action) last = ft.last_action[(int64_t)net * ft.la_s_net + pr * ft.la_s_row];
-        else if (ft.last_action64) last = (int)ft.last_action64[(int64_t)net * ft.la64_s_net + pr * ft.la64_s_row];
-    }
-    // what this column gathers: the base column the row itself, a job column the row with the job's entity replaced in the knocked sources
-    const int job = (valid && !is_base) ? ka.jobs[slot] : -1;
-    KnockCol kc;
-    kc.ent0 = (ka.knock[0] && ft.w[0] > 0) ? job : -1;
-    kc.ent1 = (ka.knock[1] && ft.w[1] > 0) ? job : -1;
-    kc.ent2 = (ka.knock[2] && ft.w[2] > 0) ? job : -1;
-    kc.bl0 = ka.baseline[0]; kc.bl1 = ka.baseline[1]; kc.bl2 = ka.baseline[2];
-    kc.ov0 = nullptr; kc.ov1 = nullptr; kc.ov2 = nullptr;
-    kc.se0 = 0; kc.se1 = 0; kc.se2 = 0;
+    const KnockTile col = knock_tile(ka, ft, tile, JT, D, net, n);           // (ac_kmap_ko.h; no override)
+    const bool valid = col.valid;
+    const int64_t ec = col.ec, sc = col.sc;
+    const int jt = col.jt;
     const KMap km = make_kmap(ft);                                           // (kfeat_ko reads the one-hot widths from it)
     const SalMap sm = sal_make_map(ft);                                      // (the K map as scalars: sal_body.h)
     const int F = sm.NW + ft.n_actions + ft.n_id, KT = sm.KT;
-    const int bw0 = sm.w0, bw1 = sm.w1, bw2 = sm.w2;
-    auto feat = [&](const KTile& kt) {
-        const int ws = kt.s == 0 ? bw0 : (kt.s == 1 ? bw1 : bw2);
-        return kfeat_ko(km, kt, p0, p1, p2, kc, ws, valid, last, net);
-    };
 
 #include "trace_trunk_impl.h"
 }
@@ -128,16 +103,11 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void ac_knockout_trace_walk_kernel
     const float* gi_row = a.gi + chain * S * PGI;                               // step s: + s * PGI
     auto gi_at = [&](int s) -> const float* { return s < D ? gi_own + (int64_t)s * JT * 16 * PGI : gi_row + (int64_t)s * PGI; };
 
-    // loop invariants.  GRU waves: W_hh rows of this wave's hidden units, gate by gate, and their bias tiles
-    f32x4 wf[3][PT], bh[3], gi[3];
-    // head wave: rnn.norm and the head
+    // loop invariants.  GRU waves: walk_gru_load (trace_body.h); head wave: rnn.norm and the head
+    WalkGru u;
     f32x4 gm[PT], bt[PT], hw[PT], hb = splat4(0.f);
     if (gru) {
-        for (int k = 0; k < 3; ++k) {
-            for (int T = 0; T < PT; ++T) wf[k][T] = wfrag_a(P + nw.off[IPLAN_AC_WHH], PM, 3 * PM, k * PM + 16 * w, 16 * T);
-            bh[k] = bfrag_a(P + nw.off[IPLAN_AC_BHH], k * PT + w);
-            gi[k] = vload_a(gi_at(0), valid, k * PT + w);
-        }
+        walk_gru_load(u, P, nw, w, gi_at(0), valid);
     } else {
         for (int t = 0; t < PT; ++t) {
             gm[t] = bfrag_a(P + nw.off[IPLAN_AC_LN3_W], t);
@@ -150,24 +120,8 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void ac_knockout_trace_walk_kernel
     float* shift = which ? ka.shift_sq_critic : ka.shift_sq_actor;
 
     for (int s = 0; s < S; ++s) {
-        f32x4 gin[3];
-        if (gru) {
-            const bool more = valid && s + 1 < S;
-            for (int k = 0; k < 3; ++k) gin[k] = vload_a(gi_at(s + 1), more, k * PT + w);
-            f32x4 acc[3] = {bh[0], bh[1], bh[2]};
-            for (int T = 0; T < PT; ++T)
-                for (int q = 0; q < 4; ++q)
-                    for (int k = 0; k < 3; ++k) acc[k] = mfma4(wf[k][T][q], h[T][q], acc[k]);
-            const f32x4 hown = w == 0 ? h[0] : (w == 1 ? h[1] : (w == 2 ? h[2] : h[3]));
-            const GruGates o = gru_gates(gi[0] + acc[0], gi[1] + acc[1], gi[2], acc[2], hown);
-            *reinterpret_cast<f32x4*>(&sh.h[s & 1][n][16 * w + 4 * g]) = o.h;
-        }
-        IPLAN_LDS_BARRIER();
-        for (int t = 0; t < PT; ++t) h[t] = *reinterpret_cast<const f32x4*>(&sh.h[s & 1][n][16 * t + 4 * g]);
-        if (gru) {
-            for (int k = 0; k < 3; ++k) gi[k] = gin[k];
-            continue;
-        }
+        walk_step(u, gru, h, sh, s, w, gi_at(s + 1), valid && s + 1 < S);
+        if (gru) continue;
         // ---- head wave: the results of step s.  Buffer s & 1 is next written behind the barrier of step s + 1, which waits for this wave
         const int64_t brow = ((int64_t)net * E + ec) * S + s;                 // the base chain's outputs
         const int64_t orow = brow * J + (jobcol ? slot : 0);                  // the column's outputs
@@ -181,81 +135,16 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void ac_knockout_trace_walk_kernel
         layer_norm_tiles_f<PT>(f, gm, bt, nullptr, nullptr);
         f32x4 lg = hb;
         for (int t = 0; t < PT; ++t) lg = mma_block(hw[t], f[t], lg);
-        if (which == 1) {
-            const float vb = __shfl(lg[0], KO_JOBS);
-            if (g == 0) {
-                if (base_out && a.values) a.values[brow] = lg[0];
-                if (jobcol) {
-                    if (ka.values_ko) ka.values_ko[orow] = lg[0];
-                    if (ka.dvalue) ka.dvalue[orow] = lg[0] - vb;
-                }
-            }
-            continue;
-        }
-        // masked categorical, the conventions of iplan_ac_trace (distributions.py:64-68); the columns share the row's avail
+        // the column's results against column 15 (knock_results, ac_kmap_ko.h); the columns share the row's avail and a*: the row's
+        // entry of actions_in, or the BASE chain's argmax of this step
         const int64_t pr = ec * a.feat.T_phys + s;
-        f32x4 x;
-        int offm = 0;
-        float m = -INFINITY;
-        for (int q = 0; q < 4; ++q) {
-            const int idx = 4 * g + q;
-            x[q] = lg[q];
-            if (idx < n_out) {
-                if (a.avail && a.avail[(int64_t)net * a.av_s_net + pr * a.av_s_row + idx] == 0) { x[q] = -1e10f; offm |= 1 << q; }
-                m = fmaxf(m, x[q]);
-            }
-        }
-        m = fmaxf(m, __shfl_xor(m, 16));
-        m = fmaxf(m, __shfl_xor(m, 32));
-        f32x4 ex;
-        float se = 0.f;
-        for (int q = 0; q < 4; ++q) { ex[q] = (4 * g + q < n_out) ? expf(x[q] - m) : 0.f; se += ex[q]; }
-        se = group_sum(se);
-        const float lse = m + logf(se);
-        f32x4 lp, pb;
-        for (int q = 0; q < 4; ++q) { lp[q] = x[q] - lse; pb[q] = ex[q] / se; }
-        // argmax of the probabilities, lowest index on ties (mode 0 of iplan_ac_fwd)
-        float best = -INFINITY;
-        for (int q = 0; q < 4; ++q)
-            if (4 * g + q < n_out) best = fmaxf(best, pb[q]);
-        best = fmaxf(best, __shfl_xor(best, 16));
-        best = fmaxf(best, __shfl_xor(best, 32));
-        int cand = 1 << 30;
-        for (int q = 3; q >= 0; --q)
-            if (4 * g + q < n_out && pb[q] == best) cand = 4 * g + q;
-        int oc = __shfl_xor(cand, 16); cand = oc < cand ? oc : cand;
-        oc = __shfl_xor(cand, 32); cand = oc < cand ? oc : cand;
-        // a*: the row's entry of actions_in, or the BASE chain's argmax of this step -- one action for every job
-        const int cand_b = __shfl(cand, KO_JOBS);
-        const int64_t want = a.actions_in ? a.actions_in[(int64_t)net * a.act_s_net + pr * a.act_s_row] : -1;
-        const int action = (want >= 0 && want < n_out) ? (int)want : cand_b;
-        float sel = 0.f;
-        for (int q = 0; q < 4; ++q)
-            if (4 * g + q == action) sel += lp[q];
-        sel = group_sum(sel);
-        const float sel_b = __shfl(sel, KO_JOBS);
-        const float kl = knock_kl(pb, lp, offm, n, n_out);
-        if (base_out && a.probs)
-            for (int q = 0; q < 4; ++q)
-                if (4 * g + q < n_out) a.probs[brow * n_out + 4 * g + q] = pb[q];
-        if (jobcol && ka.probs_ko)
-            for (int q = 0; q < 4; ++q)
-                if (4 * g + q < n_out) ka.probs_ko[orow * n_out + 4 * g + q] = pb[q];
-        if (jobcol && ka.logp_all_ko)
+        const int32_t* av = a.avail ? a.avail + (int64_t)net * a.av_s_net + pr * a.av_s_row : nullptr;
+        const int64_t want = (which == 0 && a.actions_in) ? a.actions_in[(int64_t)net * a.act_s_net + pr * a.act_s_row] : -1;
+        const KnockBaseOut bo = {a.values, a.probs, a.logp, a.greedy, ka.target_out};
+        const f32x4 lp = knock_results(ka, bo, which, lg, av, want, n_out, n, g, base_out, jobcol, brow, orow);
+        if (which == 0 && jobcol && ka.logp_all_ko)
             for (int q = 0; q < 4; ++q)
                 if (4 * g + q < n_out) ka.logp_all_ko[orow * n_out + 4 * g + q] = lp[q];
-        if (g != 0) continue;
-        if (base_out) {
-            if (a.logp) a.logp[brow] = sel;
-            if (a.greedy) a.greedy[brow] = (int64_t)cand;
-            if (ka.target_out) ka.target_out[brow] = (int64_t)action;
-        }
-        if (jobcol) {
-            if (ka.logp_ko) ka.logp_ko[orow] = sel;
-            if (ka.greedy_ko) ka.greedy_ko[orow] = (int64_t)cand;
-            if (ka.kl) ka.kl[orow] = kl;
-            if (ka.dlogp) ka.dlogp[orow] = sel - sel_b;
-        }
     }
 }
 
@@ -265,46 +154,20 @@ extern "C" int iplan_ac_knockout_trace(const IplanAcKnockoutTraceArgs* k, iplan_
     using namespace iplan;
     if (!k) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: null args");
     const IplanAcTraceArgs* a = &k->base;
-    if (a->which < 0 || a->which > 2 || a->n_agents < 1)
-        return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: bad which=%d / n_agents=%d", a->which, a->n_agents);
     if (a->E < 1) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: E=%d, at least one chain is needed", a->E);
     if (a->S < 1) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: H=%d, at least one step is needed", a->S);
     if (k->D < 1 || k->D > a->S) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: D=%d outside [1, H=%d]", k->D, a->S);
     if (a->phases < 0 || a->phases > 2) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: phases must be 0, 1 or 2 (got %d)", a->phases);
-    const IplanAcFeatures& ft = a->feat;
-    if (ft.N < 1 || ft.N > IPLAN_MAX_ENTITIES) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: N=%d outside [1,%d]", ft.N, IPLAN_MAX_ENTITIES);
-    if (ft.T != a->S || ft.T_phys < ft.T)
-        return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: feat.T=%d must equal H=%d and T_phys=%d must not be smaller", ft.T, a->S, ft.T_phys);
-    if (ft.n_actions < 0 || ft.n_id < 0 || ft.w[0] < 0 || ft.w[1] < 0 || ft.w[2] < 0 || ft.N * (ft.w[0] + ft.w[1] + ft.w[2]) + ft.n_actions + ft.n_id < 1)
-        return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: bad feature widths");
-    for (int s = 0; s < 3; ++s)
-        if (ft.w[s] > 0 && !ft.src[s]) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: feature source %d is null", s);
-    if (k->J < 1) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: J=%d, at least one job is needed", k->J);
-    if (!k->jobs || !k->jobs_host) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: the job list is missing (device and host copy)");
-    for (int s = 0; s < k->J; ++s)
-        if (k->jobs_host[s] < -1 || k->jobs_host[s] >= ft.N)
-            return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: job %d = %d outside [-1,%d)", s, k->jobs_host[s], ft.N);
+    if (const int rc = ac_rows_check("iplan_ac_knockout_trace", "H", a->feat, a->which, a->n_agents, a->S, a->actor, a->critic)) return rc;
+    if (const int rc = ac_jobs_check("iplan_ac_knockout_trace", "H", a->feat, a->E, a->S, k->J, k->jobs, k->jobs_host, k->knock, k->baseline)) return rc;
     const int64_t JT = (k->J + KO_JOBS - 1) / KO_JOBS;
-    if ((int64_t)a->E * a->S * JT > 0x7fffffff / 16)
-        return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: E * H * ceil(J / 15) = %lld tiles are too many", (long long)a->E * a->S * JT);
-    for (int s = 0; s < 3; ++s) {
-        if (k->knock[s] && ft.w[s] == 0) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: source %d is to be knocked, but it is absent", s);
-        if (k->baseline[s] && ft.w[s] == 0) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: a baseline for the absent source %d", s);
-    }
     if (a->entropy || a->h_all_actor || a->h_all_critic || a->h_last_actor || a->h_last_critic)
         return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: of base's outputs only probs, greedy, logp and values (the base chain) are written");
     bool any = false;
-    if (a->which != 1) {
-        if (a->actor.n_out < 1 || a->actor.n_out > 16) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: n_actions=%d outside [1,16]", a->actor.n_out);
-        if (!a->actor.params) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: actor parameters missing");
+    if (a->which != 1)
         any = any || a->probs || a->greedy || a->logp || k->target_out || k->probs_ko || k->logp_ko || k->greedy_ko || k->kl || k->dlogp ||
               k->shift_sq_actor || k->h_ko_actor || k->logp_all_ko;
-    }
-    if (a->which != 0) {
-        if (a->critic.n_out != 1) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: the critic's head has one output (got %d)", a->critic.n_out);
-        if (!a->critic.params) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: critic parameters missing");
-        any = any || a->values || k->values_ko || k->dvalue || k->shift_sq_critic || k->h_ko_critic;
-    }
+    if (a->which != 0) any = any || a->values || k->values_ko || k->dvalue || k->shift_sq_critic || k->h_ko_critic;
     if (a->phases != 1 && !any) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: no output of the selected nets was asked for");
     if (!k->gi_ko)
         return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: the gi_ko workspace [2, n_agents, E, D, ceil(J / 15), 16, %d] is missing", IPLAN_AC_TRACE_GI);

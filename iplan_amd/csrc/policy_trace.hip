@@ -83,18 +83,13 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void ac_trace_walk_kernel(IplanAcT
     f32x4 h[PT];
     for (int t = 0; t < PT; ++t) h[t] = h0 ? vload(h0 + (int64_t)net * a.h0_s_net + ec * a.h0_s_chain, valid, PM, t) : splat4(0.f);
 
-    // loop invariants.  GRU waves: W_hh rows of this wave's hidden units, gate by gate, and their bias tiles
-    f32x4 wf[3][PT], bh[3], gi[3];
+    // loop invariants.  GRU waves: walk_gru_load (trace_body.h); head wave: rnn.norm and the head
+    WalkGru u;
     const float* girow = a.gi + (((int64_t)which * a.n_agents + net) * E + ec) * S * PGI;     // step s: + s * PGI
-    // head wave: rnn.norm and the head
     f32x4 gm[PT], bt[PT], hw[PT], hb = splat4(0.f);
     const bool want_head = which ? a.values != nullptr : (a.probs || a.entropy || a.greedy || a.logp);
     if (gru) {
-        for (int k = 0; k < 3; ++k) {
-            for (int T = 0; T < PT; ++T) wf[k][T] = wfrag_a(P + nw.off[IPLAN_AC_WHH], PM, 3 * PM, k * PM + 16 * w, 16 * T);
-            bh[k] = bfrag_a(P + nw.off[IPLAN_AC_BHH], k * PT + w);
-            gi[k] = vload_a(girow, valid, k * PT + w);
-        }
+        walk_gru_load(u, P, nw, w, girow, valid);
     } else {
         for (int t = 0; t < PT; ++t) {
             gm[t] = bfrag_a(P + nw.off[IPLAN_AC_LN3_W], t);
@@ -107,24 +102,8 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void ac_trace_walk_kernel(IplanAcT
     float* h_last = which ? a.h_last_critic : a.h_last_actor;
 
     for (int s = 0; s < S; ++s) {
-        f32x4 gin[3];
-        if (gru) {
-            const bool more = valid && s + 1 < S;
-            for (int k = 0; k < 3; ++k) gin[k] = vload_a(girow + (int64_t)(s + 1) * PGI, more, k * PT + w);
-            f32x4 acc[3] = {bh[0], bh[1], bh[2]};
-            for (int T = 0; T < PT; ++T)
-                for (int q = 0; q < 4; ++q)
-                    for (int k = 0; k < 3; ++k) acc[k] = mfma4(wf[k][T][q], h[T][q], acc[k]);
-            const f32x4 hown = w == 0 ? h[0] : (w == 1 ? h[1] : (w == 2 ? h[2] : h[3]));
-            const GruGates o = gru_gates(gi[0] + acc[0], gi[1] + acc[1], gi[2], acc[2], hown);
-            *reinterpret_cast<f32x4*>(&sh.h[s & 1][n][16 * w + 4 * g]) = o.h;
-        }
-        IPLAN_LDS_BARRIER();
-        for (int t = 0; t < PT; ++t) h[t] = *reinterpret_cast<const f32x4*>(&sh.h[s & 1][n][16 * t + 4 * g]);
-        if (gru) {
-            for (int k = 0; k < 3; ++k) gi[k] = gin[k];
-            continue;
-        }
+        walk_step(u, gru, h, sh, s, w, girow + (int64_t)(s + 1) * PGI, valid && s + 1 < S);
+        if (gru) continue;
         // ---- head wave: the results of step s
         const int64_t orow = ((int64_t)net * E + ec) * S + s;
         if (h_all) for (int t = 0; t < PT; ++t) vstore_a(h_all + orow * PM, valid, t, h[t]);
@@ -139,52 +118,23 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void ac_trace_walk_kernel(IplanAcT
             if (valid && g == 0) a.values[orow] = lg[0];
             continue;
         }
-        // masked categorical (distributions.py:64-68, act.py:81-83,159-164), the conventions of iplan_ac_fwd
+        // the masked categorical of ac_categorical.h
         const int64_t pr = ec * a.feat.T_phys + s;
-        f32x4 x;
-        float m = -INFINITY;
-        for (int q = 0; q < 4; ++q) {
-            const int idx = 4 * g + q;
-            x[q] = lg[q];
-            if (idx < n_out) {
-                if (a.avail && valid && a.avail[(int64_t)net * a.av_s_net + pr * a.av_s_row + idx] == 0) x[q] = -1e10f;
-                m = fmaxf(m, x[q]);
-            }
-        }
-        m = fmaxf(m, __shfl_xor(m, 16));
-        m = fmaxf(m, __shfl_xor(m, 32));
-        f32x4 ex;
-        float se = 0.f;
-        for (int q = 0; q < 4; ++q) { ex[q] = (4 * g + q < n_out) ? expf(x[q] - m) : 0.f; se += ex[q]; }
-        se = group_sum(se);
-        const float lse = m + logf(se);
-        f32x4 lp, pb;
-        for (int q = 0; q < 4; ++q) { lp[q] = x[q] - lse; pb[q] = ex[q] / se; }
-        // argmax of the probabilities, lowest index on ties (mode 0 of iplan_ac_fwd)
-        float best = -INFINITY;
-        for (int q = 0; q < 4; ++q)
-            if (4 * g + q < n_out) best = fmaxf(best, pb[q]);
-        best = fmaxf(best, __shfl_xor(best, 16));
-        best = fmaxf(best, __shfl_xor(best, 32));
-        int cand = 1 << 30;
-        for (int q = 3; q >= 0; --q)
-            if (4 * g + q < n_out && pb[q] == best) cand = 4 * g + q;
-        int oc = __shfl_xor(cand, 16); cand = oc < cand ? oc : cand;
-        oc = __shfl_xor(cand, 32); cand = oc < cand ? oc : cand;
+        const MaskedCat c = masked_categorical(lg, (a.avail && valid) ? a.avail + (int64_t)net * a.av_s_net + pr * a.av_s_row : nullptr, g, n_out);
         const int action = (a.actions_in && valid) ? (int)a.actions_in[(int64_t)net * a.act_s_net + pr * a.act_s_row] : -1;
         float sel = 0.f, ent = 0.f;
         for (int q = 0; q < 4; ++q) {
             const int idx = 4 * g + q;
             if (idx < n_out) {
-                if (idx == action) sel += lp[q];
-                ent -= pb[q] * lp[q];
-                if (a.probs && valid) a.probs[orow * n_out + idx] = pb[q];
+                if (idx == action) sel += c.lp[q];
+                ent -= c.pb[q] * c.lp[q];
+                if (a.probs && valid) a.probs[orow * n_out + idx] = c.pb[q];
             }
         }
         sel = group_sum(sel);
         ent = group_sum(ent);
         if (valid && g == 0) {
-            if (a.greedy) a.greedy[orow] = (int64_t)cand;
+            if (a.greedy) a.greedy[orow] = (int64_t)c.cand;
             if (a.logp) a.logp[orow] = sel;
             if (a.entropy) a.entropy[orow] = ent;
         }
@@ -196,27 +146,16 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void ac_trace_walk_kernel(IplanAcT
 extern "C" int iplan_ac_trace(const IplanAcTraceArgs* a, iplan_stream_t stream) {
     using namespace iplan;
     if (!a) return fail(IPLAN_EINVAL, "iplan_ac_trace: null args");
-    if (a->which < 0 || a->which > 2 || a->n_agents < 1) return fail(IPLAN_EINVAL, "iplan_ac_trace: bad which=%d / n_agents=%d", a->which, a->n_agents);
     if (a->E < 1) return fail(IPLAN_EINVAL, "iplan_ac_trace: E=%d, at least one chain is needed", a->E);
     if (a->S < 1) return fail(IPLAN_EINVAL, "iplan_ac_trace: S=%d, at least one step is needed", a->S);
     if ((int64_t)a->E * a->S > 0x7fffffff / 16) return fail(IPLAN_EINVAL, "iplan_ac_trace: E * S = %lld rows are too many", (long long)a->E * a->S);
     if (a->phases < 0 || a->phases > 2) return fail(IPLAN_EINVAL, "iplan_ac_trace: phases must be 0, 1 or 2 (got %d)", a->phases);
-    const IplanAcFeatures& ft = a->feat;
-    if (ft.N < 1 || ft.N > IPLAN_MAX_ENTITIES) return fail(IPLAN_EINVAL, "iplan_ac_trace: N=%d outside [1,%d]", ft.N, IPLAN_MAX_ENTITIES);
-    if (ft.T != a->S || ft.T_phys < ft.T) return fail(IPLAN_EINVAL, "iplan_ac_trace: feat.T=%d must equal S=%d and T_phys=%d must not be smaller", ft.T, a->S, ft.T_phys);
-    if (ft.n_actions < 0 || ft.n_id < 0 || ft.w[0] < 0 || ft.w[1] < 0 || ft.w[2] < 0 || ft.N * (ft.w[0] + ft.w[1] + ft.w[2]) + ft.n_actions + ft.n_id < 1)
-        return fail(IPLAN_EINVAL, "iplan_ac_trace: bad feature widths");
-    for (int s = 0; s < 3; ++s)
-        if (ft.w[s] > 0 && !ft.src[s]) return fail(IPLAN_EINVAL, "iplan_ac_trace: feature source %d is null", s);
+    if (const int rc = ac_rows_check("iplan_ac_trace", "S", a->feat, a->which, a->n_agents, a->S, a->actor, a->critic)) return rc;
     if (a->which != 1) {
-        if (a->actor.n_out < 1 || a->actor.n_out > 16) return fail(IPLAN_EINVAL, "iplan_ac_trace: n_actions=%d outside [1,16]", a->actor.n_out);
-        if (!a->actor.params || !a->h_last_actor) return fail(IPLAN_EINVAL, "iplan_ac_trace: actor parameters or h_last_actor missing");
+        if (!a->h_last_actor) return fail(IPLAN_EINVAL, "iplan_ac_trace: h_last_actor missing");
         if (a->logp && !a->actions_in) return fail(IPLAN_EINVAL, "iplan_ac_trace: logp needs actions_in");
     }
-    if (a->which != 0) {
-        if (a->critic.n_out != 1) return fail(IPLAN_EINVAL, "iplan_ac_trace: the critic's head has one output (got %d)", a->critic.n_out);
-        if (!a->critic.params || !a->h_last_critic) return fail(IPLAN_EINVAL, "iplan_ac_trace: critic parameters or h_last_critic missing");
-    }
+    if (a->which != 0 && !a->h_last_critic) return fail(IPLAN_EINVAL, "iplan_ac_trace: h_last_critic missing");
     if (!a->gi) return fail(IPLAN_EINVAL, "iplan_ac_trace: the gi workspace [2, n_agents, E * S, %d] is missing", IPLAN_AC_TRACE_GI);
     if (!aligned16(a->gi) || !aligned16(a->h_all_actor) || !aligned16(a->h_all_critic) || !aligned16(a->h_last_actor) || !aligned16(a->h_last_critic) ||
         !aligned16(a->packed_actor) || !aligned16(a->packed_critic) || (a->packed_s_net & 3))

@@ -13,6 +13,7 @@
 #include "wave_tile.h"
 #include "gru_tile.h"
 #include "ac_kmap.h"
+#include "ac_categorical.h"
 
 namespace iplan {
 

@@ -124,48 +124,17 @@
             if (g == 0) dl[0] = 1.0f;
             if (valid && g == 0 && a.values) a.values[orow] = lg[0];
         } else {
-            // masked categorical, the conventions of iplan_ac_trace (distributions.py:64-68)
+            // the masked categorical of ac_categorical.h
             const int32_t* av = (a.avail && valid) ? a.avail + (int64_t)net * a.av_s_net + ec * a.av_s_chain + sc * a.av_s_step : nullptr;
-            f32x4 x;
-            bool off[4];
-            float m = -INFINITY;
-            for (int q = 0; q < 4; ++q) {
-                const int idx = 4 * g + q;
-                x[q] = lg[q];
-                off[q] = idx >= n_out;
-                if (idx < n_out) {
-                    if (av && av[idx] == 0) { x[q] = -1e10f; off[q] = true; }
-                    m = fmaxf(m, x[q]);
-                }
-            }
-            m = fmaxf(m, __shfl_xor(m, 16));
-            m = fmaxf(m, __shfl_xor(m, 32));
-            f32x4 ex;
-            float se = 0.f;
-            for (int q = 0; q < 4; ++q) { ex[q] = (4 * g + q < n_out) ? expf(x[q] - m) : 0.f; se += ex[q]; }
-            se = group_sum(se);
-            const float lse = m + logf(se);
-            f32x4 lp, pb;
-            for (int q = 0; q < 4; ++q) { lp[q] = x[q] - lse; pb[q] = ex[q] / se; }
-            // argmax of the probabilities, lowest index on ties
-            float best = -INFINITY;
-            for (int q = 0; q < 4; ++q)
-                if (4 * g + q < n_out) best = fmaxf(best, pb[q]);
-            best = fmaxf(best, __shfl_xor(best, 16));
-            best = fmaxf(best, __shfl_xor(best, 32));
-            int cand = 1 << 30;
-            for (int q = 3; q >= 0; --q)
-                if (4 * g + q < n_out && pb[q] == best) cand = 4 * g + q;
-            int oc = __shfl_xor(cand, 16); cand = oc < cand ? oc : cand;
-            oc = __shfl_xor(cand, 32); cand = oc < cand ? oc : cand;
+            const MaskedCat c = masked_categorical(lg, av, g, n_out);
             int64_t want = a.target_all;
             if (a.target && valid) want = a.target[(int64_t)net * a.tg_s_net + ec * a.tg_s_chain + sc * a.tg_s_step];
-            const int action = (want >= 0 && want < n_out) ? (int)want : cand;
+            const int action = (want >= 0 && want < n_out) ? (int)want : c.cand;
             float sel = 0.f;
             for (int q = 0; q < 4; ++q) {
                 const int idx = 4 * g + q;
-                if (idx == action) sel += lp[q];
-                if (!off[q]) dl[q] = (idx == action ? 1.0f : 0.0f) - pb[q];
+                if (idx == action) sel += c.lp[q];
+                if (idx < n_out && !((c.offm >> q) & 1)) dl[q] = (idx == action ? 1.0f : 0.0f) - c.pb[q];   // (no gradient into a masked logit)
             }
             sel = group_sum(sel);
             if (valid && g == 0) {

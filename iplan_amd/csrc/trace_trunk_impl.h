@@ -1,4 +1,5 @@
-// The trunk's body (trace_body.h): statements, included inside a kernel -- no include guard, no namespace.
+// The trunk's body (trace_body.h): statements, included inside a kernel -- no include guard, no namespace.  The part behind f2 (the gi
+// rows) is for the includers that name TRUNK_GI_ROW.
 
     // LayerNorm(F) statistics: mean, then the centred second moment
     float sum = 0.f;
@@ -59,6 +60,8 @@
     for (int t = 0; t < PT; ++t)
         f2[t] = trace_act4(dense_tile_ga<PT>(P + nw.off[IPLAN_AC_FC2_W], PM, PM, 16 * t, f1, bfrag_a(P + nw.off[IPLAN_AC_FC2_B], t)), tanh);
     layer_norm_tiles<PT>(f2, P + nw.off[IPLAN_AC_LN2_W], P + nw.off[IPLAN_AC_LN2_B], nullptr, nullptr);
+#ifdef TRUNK_GI_ROW
     float* girow = TRUNK_GI_ROW;
     for (int t = 0; t < 3 * PT; ++t)
         vstore_a(girow, valid, t, dense_tile_ga<PT>(P + nw.off[IPLAN_AC_WIH], PM, 3 * PM, 16 * t, f2, bfrag_a(P + nw.off[IPLAN_AC_BIH], t)));
+#endif

@@ -253,13 +253,12 @@ def gat_knockout_args(arena, src0, src1, hidden, jobs, base=None, noise=None, ta
     dev = src0.device
     want = tuple(want)
     assert want and all(k in GAT_KNOCKOUT_OUTPUTS for k in want), want
-    jobs = [int(j) for j in jobs]
-    J = len(jobs)
-    assert J >= 1 and all(-1 <= j < N for j in jobs), (jobs, N)
     k0, k1 = bool(knock[0]), bool(knock[1])
     assert not (k1 and d1 == 0), "source 1 is to be knocked, but there is none"
     a = L.GatKnockoutArgs()
-    a.n_nets, a.B, a.N, a.d0, a.d1, a.J = n_nets, B, N, d0, d1, J
+    a.n_nets, a.B, a.N, a.d0, a.d1 = n_nets, B, N, d0, d1
+    j_host, j_dev = _job_list(a, jobs, N, dev)
+    J = a.J
     a.src0 = src0.data_ptr()
     a.src0_s_net, a.src0_s_b, _ = _nbs_strides(src0.unsqueeze(2), N * d0, "src0")
     if src1 is not None:
@@ -278,9 +277,6 @@ def gat_knockout_args(arena, src0, src1, hidden, jobs, base=None, noise=None, ta
         a.base = base.data_ptr()
         a.base_s_net, a.base_s_b, _ = _nbs_strides(base.unsqueeze(2), N * A, "base")
     assert "shift_sq" not in want or base is not None, "shift_sq needs base, the latent with nothing knocked"
-    j_host = (C.c_int32 * J)(*jobs)
-    j_dev = torch.tensor(jobs, dtype=torch.int32, device=dev)
-    a.jobs, a.jobs_host = j_dev.data_ptr(), C.cast(j_host, C.c_void_p)
     a.knock0, a.knock1 = int(k0), int(k1)
     keep = [src0, src1, hidden, noise, base, j_host, j_dev]
     for which, (row, d) in enumerate(zip(baseline, (d0, d1))):
@@ -666,6 +662,79 @@ def _ac_packed(a, which, packed):
             a.packed_critic, a.packed_s_net = pc.data_ptr(), pc.stride(0)
 
 
+def _job_list(a, jobs, N, dev):
+    """``jobs``: J >= 1 entity indices in [0, N), or -1 for "nothing knocked", entered into the descriptor ``a`` (J, jobs, jobs_host) as
+    the device copy the kernel reads and the host copy the entry point checks -> both copies, to be kept alive"""
+    jobs = [int(j) for j in jobs]
+    J = len(jobs)
+    assert J >= 1 and all(-1 <= j < N for j in jobs), (jobs, N)
+    j_host = (C.c_int32 * J)(*jobs)
+    j_dev = torch.tensor(jobs, dtype=torch.int32, device=dev)
+    a.J, a.jobs, a.jobs_host = J, j_dev.data_ptr(), C.cast(j_host, C.c_void_p)
+    return j_host, j_dev
+
+
+def _per_source(seq, n_src, what):
+    """``seq`` (None: nothing) as one entry per source of the rows; it may be shorter, and longer only with nothing past the end"""
+    seq = (None,) * n_src if seq is None else tuple(seq)
+    assert all(v is None or v is False for v in seq[n_src:]), (what, "names a source the rows do not have", n_src)
+    return seq[:n_src] + (None,) * (n_src - len(seq))
+
+
+def _knock_baseline(a, spec, knock, baseline, dev):
+    """Per source of ``spec``, into the knock-out descriptor ``a``: the ``knock`` flags (None: every source) and the ``baseline`` rows
+    [w] or None (zeros); neither may name an absent source -> the rows, to be kept alive"""
+    n_src = len(spec.sources)
+    knock = (True,) * n_src if knock is None else _per_source(knock, n_src, "knock")
+    baseline = _per_source(baseline, n_src, "baseline")
+    for k, (_, w, _, _) in enumerate(spec.sources):
+        a.knock[k] = int(bool(knock[k]))
+        row = baseline[k]
+        assert w > 0 or not (a.knock[k] or row is not None), ("source", k, "is absent")
+        if row is not None:
+            assert row.shape == (w,) and row.dtype == torch.float32 and row.is_contiguous() and row.device == dev, ("baseline", k, tuple(row.shape), w)
+            a.baseline[k] = row.data_ptr()
+    return baseline
+
+
+def _pair_dests(a, which, want, dest, pair, n_actions):
+    """the per-(row, job) destinations, ``pair`` = their shape, that both policy knock-out descriptors name alike"""
+    if which != 1:
+        for k, inner, dtype in (("kl", (), torch.float32), ("dlogp", (), torch.float32), ("greedy_ko", (), torch.int64),
+                                ("probs_ko", (n_actions,), torch.float32), ("logp_ko", (), torch.float32)):
+            if k in want:
+                setattr(a, k, dest(k, pair + inner, dtype))
+    if which != 0:
+        for k in ("dvalue", "values_ko"):
+            if k in want:
+                setattr(a, k, dest(k, pair))
+
+
+def _chain_operands(a, which, n_agents, E, last_row, dev, n_actions, hidden0_actor, hidden0_critic, h_strides, avail, avail_strides, actions_in,
+                    act_strides, what="actions_in"):
+    """What a walk over E chains reads beside its rows, into the IplanAcTraceArgs ``a``: hidden0_* [.., 64] by (net, chain) (None:
+    zeros) and, by physical row, the actors' avail int32 [.., n_actions] and actions_in int64, each checked to lie inside its storage"""
+    for net, h0, key in ((0, hidden0_actor, "actor"), (1, hidden0_critic, "critic")):
+        if which == 1 - net or h0 is None:
+            continue
+        assert h0.dtype == torch.float32 and h0.device == dev and min(h_strides) >= 0
+        _inside(h0, (n_agents - 1) * h_strides[0] + (E - 1) * h_strides[1] + L.AC_HIDDEN, "hidden0_" + key)
+        setattr(a, "hidden0_" + key, h0.data_ptr())
+    a.h0_s_net, a.h0_s_chain = h_strides
+    if which == 1:
+        return
+    if avail is not None:
+        assert avail.dtype == torch.int32 and avail.device == dev and min(avail_strides) >= 0
+        _inside(avail, (n_agents - 1) * avail_strides[0] + last_row * avail_strides[1] + n_actions, "avail")
+        a.avail = avail.data_ptr()
+        a.av_s_net, a.av_s_row = avail_strides
+    if actions_in is not None:
+        assert actions_in.dtype == torch.int64 and actions_in.device == dev and min(act_strides) >= 0
+        _inside(actions_in, (n_agents - 1) * act_strides[0] + last_row * act_strides[1] + 1, what)
+        a.actions_in = actions_in.data_ptr()
+        a.act_s_net, a.act_s_row = act_strides
+
+
 def policy_trace(actor_arena, critic_arena, which, spec, E, S, n_agents, hidden0_actor=None, hidden0_critic=None, h_strides=(0, 0),
                  avail=None, avail_strides=(0, 0), actions_in=None, act_strides=(0, 0), n_actions=5,
                  want=("probs", "entropy", "greedy", "logp", "values"), packed=None, out=None, lib=None):
@@ -703,29 +772,16 @@ def policy_trace_args(actor_arena, critic_arena, which, spec, E, S, n_agents, hi
     def dest(k, shape, dtype=torch.float32):
         return _dest(out, res, k, shape, dtype, dev)
 
-    for net, h0, key in ((0, hidden0_actor, "actor"), (1, hidden0_critic, "critic")):
+    _chain_operands(a, which, n_agents, E, last_row, dev, n_actions, hidden0_actor, hidden0_critic, h_strides, avail, avail_strides, actions_in,
+                    act_strides)
+    for net, key in ((0, "actor"), (1, "critic")):
         if which == 1 - net:
             continue
-        if h0 is not None:
-            assert h0.dtype == torch.float32 and h0.device == dev and min(h_strides) >= 0
-            _inside(h0, (n_agents - 1) * h_strides[0] + (E - 1) * h_strides[1] + M, "hidden0_" + key)
-            setattr(a, "hidden0_" + key, h0.data_ptr())
         setattr(a, "h_last_" + key, dest("h_last_" + key, (n_agents, E, M)))
         if "h_" + key in want:
             setattr(a, "h_all_" + key, dest("h_" + key, (n_agents, E, S, M)))
-    a.h0_s_net, a.h0_s_chain = h_strides
     if which != 1:
         _fill_acnet(a.actor, actor_arena, L.ACTOR_PARAM_ORDER, n_actions)
-        if avail is not None:
-            assert avail.dtype == torch.int32 and avail.device == dev and min(avail_strides) >= 0
-            _inside(avail, (n_agents - 1) * avail_strides[0] + last_row * avail_strides[1] + n_actions, "avail")
-            a.avail = avail.data_ptr()
-            a.av_s_net, a.av_s_row = avail_strides
-        if actions_in is not None:
-            assert actions_in.dtype == torch.int64 and actions_in.device == dev and min(act_strides) >= 0
-            _inside(actions_in, (n_agents - 1) * act_strides[0] + last_row * act_strides[1] + 1, "actions_in")
-            a.actions_in = actions_in.data_ptr()
-            a.act_s_net, a.act_s_row = act_strides
         if "probs" in want:
             a.probs = dest("probs", (n_agents, E, S, n_actions))
         if "entropy" in want:
@@ -882,75 +938,38 @@ def policy_knockout_args(actor_arena, critic_arena, which, spec, E, S, n_agents,
     queued, checked but not launched: (IplanAcKnockoutArgs, dict, tuple)."""
     want = tuple(want)
     assert want and all(k in POLICY_KNOCKOUT_OUTPUTS for k in want), want
-    jobs = [int(j) for j in jobs]
-    J, N = len(jobs), spec.N
-    assert J >= 1 and all(-1 <= j < N for j in jobs), (jobs, N)
-    n_src = len(spec.sources)
+    N = spec.N
     # the rows, the states, avail and target as saliency describes them; its "y" outputs receive the base result
     a = L.AcKnockoutArgs()
     dev = _saliency_rows(a.base, actor_arena, critic_arena, which, spec, E, S, n_agents, h_actor, h_critic, h_strides, avail, avail_strides, target,
                          target_strides, target_all, n_actions)
     _ac_packed(a.base, which, packed)
     res = {}
-    keep = (spec, h_actor, h_critic, avail, target, packed)
 
     def dest(k, shape, dtype=torch.float32):
         return _dest(out, res, k, shape, dtype, dev)
 
     if "base" in want:
         _saliency_y(a.base, which, dest, n_agents, E, S)
-    a.J = J
-    j_host = (C.c_int32 * J)(*jobs)
-    j_dev = torch.tensor(jobs, dtype=torch.int32, device=dev)
-    a.jobs, a.jobs_host = j_dev.data_ptr(), C.cast(j_host, C.c_void_p)
-    keep = keep + (j_host, j_dev)
-
-    def per_source(seq, what):
-        seq = (None,) * n_src if seq is None else tuple(seq)
-        assert all(v is None or v is False for v in seq[n_src:]), (what, "names a source the rows do not have", n_src)
-        return seq[:n_src] + (None,) * (n_src - len(seq))
-
-    knock = (True,) * n_src if knock is None else per_source(knock, "knock")
-    baseline, override = per_source(baseline, "baseline"), per_source(override, "override")
+    keep = (spec, h_actor, h_critic, avail, target, packed) + _job_list(a, jobs, N, dev) + _knock_baseline(a, spec, knock, baseline, dev)
+    J = a.J
+    override = _per_source(override, len(spec.sources), "override")
     for k, (_, w, _, _) in enumerate(spec.sources):
-        a.knock[k] = int(bool(knock[k]))
-        assert w > 0 or not (a.knock[k] or baseline[k] is not None or override[k] is not None), ("source", k, "is absent")
-        row = baseline[k]
-        if row is not None:
-            assert row.shape == (w,) and row.dtype == torch.float32 and row.is_contiguous() and row.device == dev, ("baseline", k, tuple(row.shape), w)
-            a.baseline[k] = row.data_ptr()
         ov = override[k]
         if ov is not None:
+            assert w > 0, ("source", k, "is absent")
             assert ov.shape == (n_agents, E, S, J, N, w) and ov.dtype == torch.float32 and ov.device == dev, ("override", k, tuple(ov.shape))
             st = ov.stride()
             assert min(st) >= 0 and (st[5] == 1 or w == 1), ("override", k, "negative stride or a strided innermost axis", st)
             _inside(ov, sum((n - 1) * s for n, s in zip(ov.shape[:5], st[:5])) + w, "override")
             a.override_src[k] = ov.data_ptr()
             a.ov_s_net[k], a.ov_s_chain[k], a.ov_s_step[k], a.ov_s_job[k], a.ov_s_ent[k] = st[:5]
-        keep = keep + (row, ov)
-
-    pair = (n_agents, E, S, J)
-    if which != 1:
-        if "base" in want:
-            a.probs_base = dest("probs", (n_agents, E, S, n_actions))
-            a.greedy_base = dest("greedy", (n_agents, E, S), torch.int64)
-        if "kl" in want:
-            a.kl = dest("kl", pair)
-        if "dlogp" in want:
-            a.dlogp = dest("dlogp", pair)
-        if "greedy_ko" in want:
-            a.greedy_ko = dest("greedy_ko", pair, torch.int64)
-        if "probs_ko" in want:
-            a.probs_ko = dest("probs_ko", pair + (n_actions,))
-        if "logp_ko" in want:
-            a.logp_ko = dest("logp_ko", pair)
-    if which != 0:
-        if "dvalue" in want:
-            a.dvalue = dest("dvalue", pair)
-        if "values_ko" in want:
-            a.values_ko = dest("values_ko", pair)
+    if which != 1 and "base" in want:
+        a.probs_base = dest("probs", (n_agents, E, S, n_actions))
+        a.greedy_base = dest("greedy", (n_agents, E, S), torch.int64)
+    _pair_dests(a, which, want, dest, (n_agents, E, S, J), n_actions)
     assert res, ("nothing of", want, "is provided by the selected nets")
-    return a, res, keep
+    return a, res, keep + override
 
 
 POLICY_KNOCKOUT_TRACE_OUTPUTS = ("base", "kl", "dlogp", "dvalue", "greedy_ko", "shift_sq", "probs_ko", "logp_ko", "values_ko", "h_ko", "logp_all_ko",
@@ -982,11 +1001,8 @@ def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_age
     lib = _lib(lib)
     want = tuple(want)
     assert want and all(k in POLICY_KNOCKOUT_TRACE_OUTPUTS for k in want), want
-    jobs = [int(j) for j in jobs]
-    J, N, M = len(jobs), spec.N, L.AC_HIDDEN
-    assert J >= 1 and all(-1 <= j < N for j in jobs), (jobs, N)
+    M = L.AC_HIDDEN
     assert 1 <= D <= H, (D, H)
-    JT = (J + POLICY_KNOCKOUT_JOBS_PER_TILE - 1) // POLICY_KNOCKOUT_JOBS_PER_TILE
     n_src = len(spec.sources)
     a = L.AcKnockoutTraceArgs()
     b = a.base
@@ -994,6 +1010,9 @@ def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_age
     nets = n_agents * (2 if which == 2 else 1)
     stream = L.current_stream(dev)
     keep = [spec, hidden0_actor, hidden0_critic, avail, target, packed]
+    keep += _job_list(a, jobs, spec.N, dev)
+    J = a.J
+    JT = (J + POLICY_KNOCKOUT_JOBS_PER_TILE - 1) // POLICY_KNOCKOUT_JOBS_PER_TILE
     if D < H:
         # the rows' base gi, once per row: the plain trunk over all E x H rows (the D knocked rows' entries are not read)
         ta, _, tkeep = policy_trace_args(actor_arena, critic_arena, which, spec, E, H, n_agents, n_actions=n_actions, want=(), packed=packed)
@@ -1006,75 +1025,33 @@ def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_age
     def dest(k, shape, dtype=torch.float32):
         return _dest(out, res, k, shape, dtype, dev)
 
-    for net, h0, key in ((0, hidden0_actor, "actor"), (1, hidden0_critic, "critic")):
-        if which == 1 - net or h0 is None:
-            continue
-        assert h0.dtype == torch.float32 and h0.device == dev and min(h_strides) >= 0
-        _inside(h0, (n_agents - 1) * h_strides[0] + (E - 1) * h_strides[1] + M, "hidden0_" + key)
-        setattr(b, "hidden0_" + key, h0.data_ptr())
-    b.h0_s_net, b.h0_s_chain = h_strides
-    a.D, a.J = D, J
-    j_host = (C.c_int32 * J)(*jobs)
-    j_dev = torch.tensor(jobs, dtype=torch.int32, device=dev)
-    a.jobs, a.jobs_host = j_dev.data_ptr(), C.cast(j_host, C.c_void_p)
-    keep += [j_host, j_dev]
-    knock = (True,) * n_src if knock is None else tuple(knock)
-    baseline = (None,) * n_src if baseline is None else tuple(baseline)
-    assert len(knock) == n_src and len(baseline) == n_src, (knock, baseline, n_src)
-    for k, (_, w, _, _) in enumerate(spec.sources):
-        a.knock[k] = int(bool(knock[k]))
-        assert w > 0 or not (a.knock[k] or baseline[k] is not None), ("source", k, "is absent")
-        row = baseline[k]
-        if row is not None:
-            assert row.shape == (w,) and row.dtype == torch.float32 and row.is_contiguous() and row.device == dev, ("baseline", k, tuple(row.shape), w)
-            a.baseline[k] = row.data_ptr()
-            keep.append(row)
+    _chain_operands(b, which, n_agents, E, last_row, dev, n_actions, hidden0_actor, hidden0_critic, h_strides, avail, avail_strides, target,
+                    target_strides, what="target")
+    a.D = D
+    assert (knock is None or len(knock) == n_src) and (baseline is None or len(baseline) == n_src), (knock, baseline, n_src)
+    keep += _knock_baseline(a, spec, knock, baseline, dev)
     pair = (n_agents, E, H, J)
+    _pair_dests(a, which, want, dest, pair, n_actions)
     if which != 1:
         _fill_acnet(b.actor, actor_arena, L.ACTOR_PARAM_ORDER, n_actions)
-        if avail is not None:
-            assert avail.dtype == torch.int32 and avail.device == dev and min(avail_strides) >= 0
-            _inside(avail, (n_agents - 1) * avail_strides[0] + last_row * avail_strides[1] + n_actions, "avail")
-            b.avail = avail.data_ptr()
-            b.av_s_net, b.av_s_row = avail_strides
-        if target is not None:
-            assert target.dtype == torch.int64 and target.device == dev and min(target_strides) >= 0
-            _inside(target, (n_agents - 1) * target_strides[0] + last_row * target_strides[1] + 1, "target")
-            b.actions_in = target.data_ptr()
-            b.act_s_net, b.act_s_row = target_strides
         if "base" in want:
             b.probs = dest("probs", (n_agents, E, H, n_actions))
             b.greedy = dest("greedy", (n_agents, E, H), torch.int64)
             b.logp = dest("logp", (n_agents, E, H))
             a.target_out = dest("target_action", (n_agents, E, H), torch.int64)
-        if "kl" in want:
-            a.kl = dest("kl", pair)
-        if "dlogp" in want:
-            a.dlogp = dest("dlogp", pair)
-        if "greedy_ko" in want:
-            a.greedy_ko = dest("greedy_ko", pair, torch.int64)
-        if "probs_ko" in want:
-            a.probs_ko = dest("probs_ko", pair + (n_actions,))
-        if "logp_ko" in want:
-            a.logp_ko = dest("logp_ko", pair)
         if "logp_all_ko" in want:
             a.logp_all_ko = dest("logp_all_ko", pair + (n_actions,))
-        if "shift_sq" in want:
-            a.shift_sq_actor = dest("shift_sq_actor", pair)
-        if "h_ko" in want:
-            a.h_ko_actor = dest("h_ko_actor", pair + (M,))
     if which != 0:
         _fill_acnet(b.critic, critic_arena, L.CRITIC_PARAM_ORDER, 1)
         if "base" in want:
             b.values = dest("values", (n_agents, E, H))
-        if "dvalue" in want:
-            a.dvalue = dest("dvalue", pair)
-        if "values_ko" in want:
-            a.values_ko = dest("values_ko", pair)
+    for net, key in ((0, "actor"), (1, "critic")):
+        if which == 1 - net:
+            continue
         if "shift_sq" in want:
-            a.shift_sq_critic = dest("shift_sq_critic", pair)
+            setattr(a, "shift_sq_" + key, dest("shift_sq_" + key, pair))
         if "h_ko" in want:
-            a.h_ko_critic = dest("h_ko_critic", pair + (M,))
+            setattr(a, "h_ko_" + key, dest("h_ko_" + key, pair + (M,)))
     assert res, ("nothing of", want, "is provided by the selected nets")
     _ac_packed(b, which, packed)
     gi_shape = (2, n_agents, E, D, JT, 16, L.AC_TRACE_GI)

@@ -173,10 +173,10 @@ class Case:
         self.order = torch.arange(self.dims[1]) if order is None else torch.as_tensor(order)
         self.dbuf = {k: v[self.order].contiguous().to(self.device) for k, v in self.buf.items()}
 
-    def run(self, s0=0, s1=None, hidden="buffer", avail=True, which=2, want=OUTS, packed=True, out=None, actions=True):
-        """ops.policy_trace over steps s0 .. s1 - 1.  hidden: "buffer" (the hidden rows of step 0), None, or (actor, critic) [nA,E,M]"""
+    def operands(self, s0=0, s1=None):
+        """what the ops over steps s0 .. s1 - 1 read, as views into the device buffers: (spec, the hidden rows of step 0 (actor, critic)
+        [E, nA, M], avail [E, S', nA, n_act] int32, the recorded actions [E, S', nA] int64)"""
         nA, _, S, N, d, n_act = self.dims
-        E = len(self.order)
         s1 = S if s1 is None else s1
         a, D = self.args, self.dbuf
         srcs = []
@@ -188,16 +188,21 @@ class Case:
         spec = ops.AcFeatureSpec(N, srcs, n_actions=n_act if a.obs_last_action else 0, last_action=last if a.obs_last_action else None,
                                  la_strides=(last.stride(2), last.stride(1)), n_id=nA if a.obs_agent_id else 0, T=s1 - s0, T_phys=S + 1)
         assert spec.F == self.mac.input_shape
+        return spec, (D["ha"][:, 0, :, 4:4 + M], D["hc"][:, 0, :, 4:4 + M]), D["avail"][:, s0:s1, :, 1:1 + n_act], D["actions"][:, s0:s1, :, 1]
+
+    def run(self, s0=0, s1=None, hidden="buffer", avail=True, which=2, want=OUTS, packed=True, out=None, actions=True):
+        """ops.policy_trace over steps s0 .. s1 - 1.  hidden: "buffer" (the hidden rows of step 0), None, or (actor, critic) [nA,E,M]"""
+        nA, _, S, N, d, n_act = self.dims
+        E = len(self.order)
+        s1 = S if s1 is None else s1
+        spec, (ha, hc), av, ac = self.operands(s0, s1)
         if isinstance(hidden, str):
-            ha, hc = D["ha"][:, 0, :, 4:4 + M], D["hc"][:, 0, :, 4:4 + M]         # [E, nA, M] views
             hs = (ha.stride(1), ha.stride(0))
         elif hidden is None:
             ha, hc, hs = None, None, (0, 0)
         else:
             ha, hc = hidden
             hs = (ha.stride(0), ha.stride(1))
-        av = D["avail"][:, s0:s1, :, 1:1 + n_act]
-        ac = D["actions"][:, s0:s1, :, 1]
         res = ops.policy_trace(self.mac.actor_arena, self.mac.critic_arena, which, spec, E, s1 - s0, nA, hidden0_actor=ha, hidden0_critic=hc, h_strides=hs,
                                avail=av if avail else None, avail_strides=(av.stride(2), av.stride(1)), actions_in=ac if actions else None,
                                act_strides=(ac.stride(2), ac.stride(1)), n_actions=n_act, want=want,
@@ -440,6 +445,58 @@ def check_agrees_with_ac_forward(device, dims=(2, 17, 1, 3, 5, 5)):
     assert_vs_fp64(step, r64, r32, worst, "ac_forward")
     assert_vs_fp64(tr, r64, r32, worst, "trace", scale=2.0, other=step)
     return worst
+
+
+def check_one_categorical(device, n_act):
+    """7b: the four inspection ops share one statement of the masked categorical (csrc/ac_categorical.h) behind the same forward
+    arithmetic, so on the same rows from the same given state -- nA = 2, E = 2, S = 1, N = 3 -- they give the same BITS: ops.policy_trace,
+    ops.saliency(want=("y",)), ops.policy_knockout(want=("base",)) and ops.policy_knockout_trace(want=("base",), H = D = 1).  n_act = 3
+    leaves a lane's four-slot group partly empty.  Row (e 0, agent 0) has every action available, (0, 1) a single one, (1, 0) none (the
+    uniform distribution), (1, 1) whatever the case drew.  Compared pairwise, with the recorded action as a*: logp and values of all
+    four, probs and greedy of the three that return them, target_action of the three that return it; with a* = the row's own argmax:
+    logp and target_action of the three that take such a target, and that target against policy_trace's greedy."""
+    dims = (2, 2, 1, 3, 5, n_act)
+    nA, E, S, N = dims[:4]
+    case = Case(dims, device, seed=3)                                              # (not the shared one: its avail is edited)
+    acts = case.buf["actions"][:, :S, :, 1]
+    av = case.buf["avail"][:, :S, :, 1:1 + n_act]
+    av[0, 0, 0] = 1
+    av[0, 0, 1] = 0
+    av[0, 0, 1, acts[0, 0, 1]] = 1
+    av[1, 0, 0] = 0
+    case.upload()
+    mac = case.mac
+    spec, (ha, hc), avail, actions = case.operands()
+    packed = mac.fc1_pack.get(spec)
+    hs2, hs3 = (ha.stride(1), ha.stride(0)), (ha.stride(1), ha.stride(0), 0)
+    by_row = lambda t: (t.stride(2), t.stride(1))                                  # noqa: E731
+    esn = lambda t: (t.stride(2), t.stride(0), t.stride(1))                        # noqa: E731
+    greedy_tgt = torch.full_like(case.dbuf["actions"], -1)[:, :S, :, 1]               # (addressed by physical row, like the recorded ones)
+    got = {}
+    for tag, tgt in (("recorded", actions), ("greedy", greedy_tgt)):
+        res = {"trace": case.run(want=("probs", "logp", "greedy", "values"))} if tag == "recorded" else {}
+        res["saliency"] = ops.saliency(mac.actor_arena, mac.critic_arena, 2, spec, E, S, nA, h_actor=ha, h_critic=hc, h_strides=hs3, avail=avail,
+                                       avail_strides=esn(avail), target=tgt, target_strides=esn(tgt), n_actions=n_act, want=("y",), packed=packed)
+        res["knockout"] = ops.policy_knockout(mac.actor_arena, mac.critic_arena, 2, spec, E, S, nA, [1], h_actor=ha, h_critic=hc, h_strides=hs3,
+                                              avail=avail, avail_strides=esn(avail), target=tgt, target_strides=esn(tgt), n_actions=n_act,
+                                              want=("base",), packed=packed)
+        res["knockout_trace"] = ops.policy_knockout_trace(mac.actor_arena, mac.critic_arena, 2, spec, E, S, S, nA, [1], hidden0_actor=ha,
+                                                          hidden0_critic=hc, h_strides=hs2, avail=avail, avail_strides=by_row(avail), target=tgt,
+                                                          target_strides=by_row(tgt), n_actions=n_act, want=("base",), packed=packed)
+        _sync(device)
+        got[tag] = res
+        for k, n_ops in (("logp", 3), ("values", 3), ("probs", 2), ("greedy", 2), ("target_action", 3)):
+            have = [n for n in sorted(res) if k in res[n]]
+            assert len(have) == n_ops + (tag == "recorded" and k != "target_action"), (tag, k, have)
+            for n in have[1:]:
+                assert torch.equal(_bits(res[have[0]][k]), _bits(res[n][k])), (tag, k, have[0], n, "bits differ")
+    rec, gr = got["recorded"], got["greedy"]
+    assert torch.equal(rec["saliency"]["target_action"].cpu(), acts.permute(2, 0, 1))
+    assert torch.equal(gr["saliency"]["target_action"], rec["trace"]["greedy"]), "a* = the row's argmax"
+    # the rows are what the docstring says they are
+    p = rec["trace"]["probs"].cpu()                                                # [nA, E, S, n_act]
+    assert (p[0, 0, 0] > 0).all() and (p[1, 0, 0] > 0).sum() == 1 and torch.equal(p[0, 1, 0], torch.full((n_act,), 1.0 / n_act))
+    return {}
 
 
 def check_repeatable(device, reps, dims=(2, 2, 3, 3, 5, 5)):

@@ -43,6 +43,11 @@ def test_trace_agrees_with_one_step_kernel():
     PC.check_agrees_with_ac_forward("cpu")
 
 
+@pytest.mark.parametrize("n_act", [5, 3])
+def test_inspection_ops_share_one_categorical(n_act):
+    PC.check_one_categorical("cpu", n_act)
+
+
 def test_trace_repeatable():
     PC.check_repeatable("cpu", 2)
 

@@ -39,6 +39,11 @@ def test_trace_agrees_with_one_step_kernel():
     _log("policy_trace_vs_ac_forward", PC.check_agrees_with_ac_forward(DEV))
 
 
+@pytest.mark.parametrize("n_act", [5, 3])
+def test_inspection_ops_share_one_categorical(n_act):
+    PC.check_one_categorical(DEV, n_act)
+
+
 def test_trace_repeatable():
     PC.check_repeatable(DEV, 20)
 
