@@ -1390,6 +1390,57 @@ typedef struct {
 int iplan_gat_knockout(const IplanGatKnockoutArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Neighbour knock-out through time: iplan_gat_trace's walk, run once per JOB with one entity's input row replaced in the first D
+ * steps of the window (csrc/gat_knockout_trace.hip).  One 512-thread workgroup owns one (net, b, job slot) (grid n_nets*B*J) and
+ * walks steps start .. start + H - 1 of the episode fields, read in place through net / b / step strides and never written:
+ * h_s = GAT(x_s, h_{s-1}), h_{start-1} = hidden0 (NULL: zeros).  In steps start .. start + D - 1 the slot's job is knocked as
+ * iplan_gat_knockout knocks it (knock0 / knock1, baseline0 / baseline1); the later steps see the recorded rows, and only the slot's
+ * own carried latent remembers the knock.  Entity j's hidden row is never overwritten.  A slot's arithmetic is iplan_gat_trace's
+ * step, so latent_ko of job j carries the bits iplan_gat_trace gives on a copy of the fields with row j replaced in the knocked steps.
+ *   jobs / jobs_host  as in IplanGatKnockoutArgs: entity indices in [0, N) or -1 (nothing knocked), duplicates allowed
+ *   noise             gumbel samples [n_nets, B, H, N, N-1, 2] contiguous (the window's), the same for every job; NULL = none
+ * Outputs, each optional (NULL = not wanted; at least one is), element (net, b, slot, step h of the window) at
+ * ptr + net*s_net + b*s_b + slot*s_job + h*s_step:
+ *   latent_ko [N, A]  the attention latent of the knocked chain (16-byte aligned, strides % 4 == 0)
+ *   attn_ko   [N, N]  the entity-indexed soft * hard map of the knocked chain, diagonal 0
+ *   shift_sq  [N]     sum_c (latent_ko[i, c] - base[i, c])^2 as IplanGatKnockoutArgs forms it.  Needs `base`: rows (net, b, h, i) at
+ *                     base + net*base_s_net + b*base_s_b + h*base_s_step + i*A, the walk with nothing knocked over the same window,
+ *                     written by an EARLIER launch (iplan_gat_trace's `latent`).
+ * No atomics, no sums across workgroups: a slot's bits depend on its scene, its job and the arguments only.
+ * Refused: N outside [2, IPLAN_MAX_ENTITIES], J < 1, H < 1, D outside [1, H], start < 0, a job outside [-1, N-1] (checked on
+ * jobs_host), knock1 with d1 == 0, null or misaligned tensors, no output, shift_sq without base, more than 2^31 - 1 workgroups.
+ */
+typedef struct {
+    int32_t n_nets, B, N, d0, d1, J, H, D, start;
+    const float* src0;
+    int64_t src0_s_net, src0_s_b, src0_s_step;
+    const float* src1;          /* may be NULL iff d1 == 0                                                 */
+    int64_t src1_s_net, src1_s_b, src1_s_step;
+    const float* hidden0;       /* the state step `start` starts from, or NULL                             */
+    int64_t h_s_net, h_s_b;
+    const float* noise;
+    const float* params;        /* parameter arena, IPLAN_GAT_* offsets                                    */
+    int64_t params_s_net;
+    int64_t off[IPLAN_GAT_NPARAM];
+    float tau;
+    int32_t knock0, knock1;
+    const int32_t* jobs;        /* [J] device memory                                                       */
+    const int32_t* jobs_host;   /* the same values in host memory (argument checks)                        */
+    const float* baseline0;     /* [d0] or NULL                                                            */
+    const float* baseline1;     /* [d1] or NULL                                                            */
+    const float* base;          /* the latents of the window with nothing knocked, or NULL                 */
+    int64_t base_s_net, base_s_b, base_s_step;
+    float* latent_ko;
+    int64_t lat_s_net, lat_s_b, lat_s_job, lat_s_step;
+    float* attn_ko;
+    int64_t attn_s_net, attn_s_b, attn_s_job, attn_s_step;
+    float* shift_sq;
+    int64_t shift_s_net, shift_s_b, shift_s_job, shift_s_step;
+} IplanGatKnockoutTraceArgs;
+
+int iplan_gat_knockout_trace(const IplanGatKnockoutTraceArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Policy knock-out (occlusion attribution of the actors and critics): every row (e, s, agent) of a recorded batch is run once per
  * JOB, forward only -- LN(F) -> fc1 -> act -> LN -> fc2 -> act -> LN -> GRU cell (state given, held) -> LN -> head -> masked softmax | V
  * -- with one entity's columns of the selected per-entity sources replaced AS THE FEATURES ARE GATHERED (csrc/policy_knockout.hip,

@@ -54,7 +54,8 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_ac_xhat_pack", "iplan_ac_fc1_split_fwd", "iplan_ac_bwd_fc1_split",
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
                 "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
-                "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout", "iplan_ac_knockout_trace"]
+                "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout", "iplan_ac_knockout_trace",
+                "iplan_gat_knockout_trace"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -474,6 +475,22 @@ class GatKnockoutArgs(C.Structure):
     ]
 
 
+class GatKnockoutTraceArgs(C.Structure):
+    _fields_ = [
+        ("n_nets", i32), ("B", i32), ("N", i32), ("d0", i32), ("d1", i32), ("J", i32), ("H", i32), ("D", i32), ("start", i32),
+        ("src0", fp), ("src0_s_net", i64), ("src0_s_b", i64), ("src0_s_step", i64),
+        ("src1", fp), ("src1_s_net", i64), ("src1_s_b", i64), ("src1_s_step", i64),
+        ("hidden0", fp), ("h_s_net", i64), ("h_s_b", i64),
+        ("noise", fp), ("params", fp), ("params_s_net", i64), ("off", i64 * GAT_NPARAM), ("tau", C.c_float),
+        ("knock0", i32), ("knock1", i32), ("jobs", fp), ("jobs_host", fp),
+        ("baseline0", fp), ("baseline1", fp),
+        ("base", fp), ("base_s_net", i64), ("base_s_b", i64), ("base_s_step", i64),
+        ("latent_ko", fp), ("lat_s_net", i64), ("lat_s_b", i64), ("lat_s_job", i64), ("lat_s_step", i64),
+        ("attn_ko", fp), ("attn_s_net", i64), ("attn_s_b", i64), ("attn_s_job", i64), ("attn_s_step", i64),
+        ("shift_sq", fp), ("shift_s_net", i64), ("shift_s_b", i64), ("shift_s_job", i64), ("shift_s_step", i64),
+    ]
+
+
 PDEC_SAL_MAX_P = 30      # IPLAN_PDEC_SAL_MAX_P
 
 
@@ -585,4 +602,5 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanAcSaliencyArgs": AcSaliencyArgs, "IplanAcSaliencyLagArgs": AcSaliencyLagArgs,
                   "IplanEncSaliencyArgs": EncSaliencyArgs, "IplanGatSaliencyArgs": GatSaliencyArgs,
                   "IplanPdecSaliencyArgs": PdecSaliencyArgs, "IplanGatKnockoutArgs": GatKnockoutArgs,
-                  "IplanAcKnockoutArgs": AcKnockoutArgs, "IplanAcKnockoutTraceArgs": AcKnockoutTraceArgs}
+                  "IplanAcKnockoutArgs": AcKnockoutArgs, "IplanAcKnockoutTraceArgs": AcKnockoutTraceArgs,
+                  "IplanGatKnockoutTraceArgs": GatKnockoutTraceArgs}

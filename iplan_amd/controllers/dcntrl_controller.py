@@ -682,8 +682,8 @@ class DcntrlMAC:
         bits, and so do a shorter ``horizon`` (a prefix), packed or in-place fc1 and any ``want``.  A job whose replaced values equal
         the originals has kl = dlogp = dvalue = state_shift = 0.0 at every step.  Device tensors in -> device tensors out, numpy in ->
         numpy out.  Draws from no generator; parameters, gradient entries, optimiser state, ``hidden_states`` and the batch are not
-        touched.  Not covered: a per-job ``override`` of a source (the chain from an ``attention_knockout`` through time, which does
-        not exist yet), re-deciding the teacher-forced last action, knocking the state itself, data-parallel aggregation, and
+        touched.  Not covered: a per-job ``override`` of a source (the chain from ``attention_knockout_trace``'s ``latent_ko``:
+        the kernel has no such argument yet), re-deciding the teacher-forced last action, knocking the state itself, data-parallel aggregation, and
         layer_N / recurrent_N other than 1."""
         a = self.args
         want, ents, srcs, widths = self._knock_request("knockout_trace", want, entities, sources, which, presence_col, max_workspace_mb,

@@ -17,24 +17,11 @@
 #include "api_util.h"
 #include "wave_tile.h"
 #include "gat_body.h"
+#include "knock_shift.h"
 
 namespace iplan {
 
 static_assert(sizeof(GatShared) <= 160 * 1024, "one CU's LDS");
-
-// sum_c (x[c] - base[c])^2 over the GH columns, c ascending.  Every difference, product and sum is rounded on its own: the whole
-// function is compiled with contraction off (the __fmul_rn / __fadd_rn of the HIP headers are plain operators compiled under the
-// default -ffp-contract=fast and would fuse again once inlined), so the plain fp32 host loop gives the same bits.
-__device__ __forceinline__ float knock_shift_sq(const float* x, const float* base) {
-#pragma clang fp contract(off)
-    float s = 0.f;
-    for (int c = 0; c < GH; ++c) {
-        const float d = x[c] - base[c];
-        const float p = d * d;
-        s = s + p;
-    }
-    return s;
-}
 
 // what the kernel itself reads of IplanGatKnockoutArgs: the scene's inputs travel in IplanGatFwdArgs, jobs_host stays on the host
 struct GatKnockoutDev {

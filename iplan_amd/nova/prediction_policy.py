@@ -471,6 +471,48 @@ class Prediction_policy:
         return {k: v.cpu().numpy() for k, v in res.items()} if as_np else res
 
     # ---------------------------------------------------------------------------- neighbour knock-out
+    def _knock_spec(self, who, N, d, sources, want, noise, deterministic, tau, presence_col, entities, baseline):
+        """the arguments ``attention_knockout`` and ``attention_knockout_trace`` share, checked (ValueError) and normalised ->
+        (sources, knock flags per source, want, tau, the job list, the baseline rows [history, behaviour] on the device or None)"""
+        sources = (sources,) if isinstance(sources, str) else tuple(sources)
+        if not sources or any(s not in ("history", "behavior") for s in sources):
+            raise ValueError(f"{who}: sources={sources} -- 'history', 'behavior' or both")
+        if "behavior" in sources and not self.args.GAT_use_behavior:
+            raise ValueError(f"{who}: sources={sources}, but this policy's GAT reads no behaviour latent (GAT_use_behavior is off)")
+        knock = ("history" in sources, "behavior" in sources)
+        want = tuple(want)
+        if any(k not in ("shift", "latent_ko", "attention_ko") for k in want):
+            raise ValueError(f"{who}: want={want} -- known: 'shift', 'latent_ko', 'attention_ko'")
+        if deterministic and noise is not None:
+            raise ValueError(f"{who}: noise was given together with deterministic=True")
+        tau = 0.01 if tau is None else float(tau)
+        if not tau > 0:
+            raise ValueError(f"{who}: tau={tau} must be positive")
+        if not isinstance(presence_col, (int, np.integer)) or presence_col >= d:
+            raise ValueError(f"{who}: presence_col={presence_col!r} outside the {d} columns")
+        if entities is None:
+            entities = range(N)
+        try:
+            jobs = list(entities)
+        except TypeError:
+            raise ValueError(f"{who}: entities={entities!r} -- None or a list of entity indices") from None
+        if not jobs or any(isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= j < N for j in jobs):
+            raise ValueError(f"{who}: entities={jobs} -- ints in [0, {N}), at least one")
+        jobs = [int(j) for j in jobs]
+        Z = self.args.latent_dim if self.args.GAT_use_behavior else 0
+        rows = [None, None]
+        if baseline is not None:
+            if not isinstance(baseline, (tuple, list)) or len(baseline) != 2:
+                raise ValueError(f"{who}: baseline -- None or a pair (row [{d}] or None, row [{Z}] or None)")
+            for s, (row, width) in enumerate(zip(baseline, (d, Z))):
+                if row is None:
+                    continue
+                row = _as_dev(torch.as_tensor(row), self.device).contiguous()
+                if row.shape != (width,) or width == 0:
+                    raise ValueError(f"{who}: baseline[{s}] {tuple(row.shape)} != {(width,)}")
+                rows[s] = row
+        return sources, knock, want, tau, jobs, rows
+
     def attention_knockout(self, history, behavior_latent=None, hidden=None, entities=None, sources=("history", "behavior"), baseline=None,
                            noise=None, deterministic=True, tau=None, want=("shift",), forecast=False, pos=(1, 2), presence_col=0,
                            max_workspace_mb=256):
@@ -503,7 +545,7 @@ class Prediction_policy:
         chunking.  numpy in -> numpy out, device tensors in -> device tensors out.  Parameters, gradients, optimiser state, carried
         state and (with ``deterministic=True``) torch's generator are not touched.  Not covered: deleting an entity from the pair chain
         (the row is replaced, which is what the environment would have shown), knocking the hidden state, continuation into the
-        actors and critics, effects carried through time, aggregation across data-parallel ranks."""
+        actors and critics, aggregation across data-parallel ranks (effects carried through time: ``attention_knockout_trace``)."""
         who = "attention_knockout"
         as_np = isinstance(history, np.ndarray)
         dev = self.device
@@ -515,48 +557,13 @@ class Prediction_policy:
         if nA != self.n_agents or d != self.obs_shape or not 2 <= N <= ops.L.GAT_MAX_ENTITIES:
             raise ValueError(f"{who}: history {tuple(hist.shape)} does not fit n_agents={self.n_agents}, obs width {self.obs_shape}, "
                              f"2 <= N <= {ops.L.GAT_MAX_ENTITIES}")
-        sources = (sources,) if isinstance(sources, str) else tuple(sources)
-        if not sources or any(s not in ("history", "behavior") for s in sources):
-            raise ValueError(f"{who}: sources={sources} -- 'history', 'behavior' or both")
-        if "behavior" in sources and not self.args.GAT_use_behavior:
-            raise ValueError(f"{who}: sources={sources}, but this policy's GAT reads no behaviour latent (GAT_use_behavior is off)")
-        knock = ("history" in sources, "behavior" in sources)
-        want = tuple(want)
-        if any(k not in ("shift", "latent_ko", "attention_ko") for k in want):
-            raise ValueError(f"{who}: want={want} -- known: 'shift', 'latent_ko', 'attention_ko'")
-        if deterministic and noise is not None:
-            raise ValueError(f"{who}: noise was given together with deterministic=True")
-        tau = 0.01 if tau is None else float(tau)
-        if not tau > 0:
-            raise ValueError(f"{who}: tau={tau} must be positive")
-        if not isinstance(presence_col, (int, np.integer)) or presence_col >= d:
-            raise ValueError(f"{who}: presence_col={presence_col!r} outside the {d} columns")
-        if entities is None:
-            entities = range(N)
-        try:
-            jobs = list(entities)
-        except TypeError:
-            raise ValueError(f"{who}: entities={entities!r} -- None or a list of entity indices") from None
-        if not jobs or any(isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= j < N for j in jobs):
-            raise ValueError(f"{who}: entities={jobs} -- ints in [0, {N}), at least one")
-        jobs = [int(j) for j in jobs]
+        sources, knock, want, tau, jobs, rows = self._knock_spec(who, N, d, sources, want, noise, deterministic, tau, presence_col, entities, baseline)
         J = len(jobs)
         pos = tuple(pos) if forecast else ()
         if forecast and (not pos or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c < d for c in pos)):
             raise ValueError(f"{who}: pos={pos} -- columns in [0, {d}), at least one")
         B = E * S
         Z = self.args.latent_dim if self.args.GAT_use_behavior else 0
-        rows = [None, None]
-        if baseline is not None:
-            if not isinstance(baseline, (tuple, list)) or len(baseline) != 2:
-                raise ValueError(f"{who}: baseline -- None or a pair (row [{d}] or None, row [{Z}] or None)")
-            for s, (row, width) in enumerate(zip(baseline, (d, Z))):
-                if row is None:
-                    continue
-                row = _as_dev(torch.as_tensor(row), dev).contiguous()
-                if row.shape != (width,) or width == 0:
-                    raise ValueError(f"{who}: baseline[{s}] {tuple(row.shape)} != {(width,)}")
-                rows[s] = row
         if hist.stride(4) != 1 or hist.stride(3) != d:
             hist = hist.contiguous()
         src0 = hist.permute(2, 0, 1, 3, 4).reshape(nA, B, N, d)                   # rows (agent, env * S + step): a view where the layout allows
@@ -672,6 +679,162 @@ class Prediction_policy:
                 summary[:, col] = np.where(cnt > 0, tot / np.maximum(cnt, 1.0), np.nan)
         final = {k: (v.cpu().numpy() if as_np else v) for k, v in final.items()}
         final["knocked"] = jn
+        if keep_shift:
+            final["summary"] = summary
+        return final
+
+    def attention_knockout_trace(self, history, behavior_latent=None, hidden0=None, entities=None, start=0, duration=1, horizon=None,
+                                 sources=("history", "behavior"), baseline=None, noise=None, deterministic=True, tau=None, want=("shift",),
+                                 presence_col=0, max_workspace_mb=256):
+        """How long does the social context remember a vehicle?  Vehicle j is out of sight for ``duration`` = D steps from step
+        ``start`` and visible again afterwards; the GAT walks steps start .. start + H - 1 (``horizon`` = H, None: up to the last step
+        of ``history``; ``duration`` None: knocked throughout, D = H) once per entity j of ``entities`` (default: all N; duplicates
+        allowed) and once with nothing knocked, every chain carrying its OWN latent: latent_s = GAT(history_s, behavior_latent_s,
+        latent_{s-1}).  In the first D steps entity j's input row is replaced as ``attention_knockout`` replaces it; the later steps
+        see the recorded rows, and only the chain's carried latent remembers the knock (the echo).  ``history`` [E,S,nA,N,d] and
+        ``behavior_latent`` [E,S,nA,N,Z] (needed with ``GAT_use_behavior``, ignored without) are aligned as in ``attention_trace``
+        and read in place; ``hidden0`` [E,nA,N,A] is the state step ``start`` starts from (None: zeros) -- for a replayed rollout with
+        ``attention_trace``'s alignment (``history[:, 1:]``, ``behavior_latent[:, :-1]``) that is ``attention_latent[:, start]``.
+        Entity j's hidden row is never overwritten.  ``sources``, ``baseline``, ``entities``, ``tau``, ``noise`` and ``deterministic``
+        mean what they mean in ``attention_knockout``; ``noise`` is [nA,E,H,N,N-1,2], the window's samples, used for the base walk AND
+        for every knocked chain (common random numbers).
+        Per chunk of environments one ``iplan_gat_trace`` launch walks the window with nothing knocked, then ``iplan_gat_knockout_trace``
+        (one workgroup per (agent, env, job) for the whole window) walks the jobs.  Returns a dict; pair tensors are indexed [ego i,
+        knocked entity], J = len(entities):
+          ``latent`` [E,H,nA,N,A]           nothing knocked: bit for bit ``attention_trace``'s on the window
+          ``latent_shift`` [E,H,nA,N,J]     with "shift" in ``want`` (the default): ||latent_ko[j][i] - latent[i]||_2 per step, torch's sqrt
+                                            of the kernel's sum of squares (columns ascending, every product and sum rounded on its own)
+          ``knocked``, ``sources``, ``window``   the entity list (int64 numpy [J]), the sources, (start, D, H)
+          ``latent_ko`` [E,H,nA,J,N,A], ``attention_ko`` [E,H,nA,J,N,N]   with "latent_ko" / "attention_ko" in ``want``: the knocked chains'
+                                            latents and entity-indexed soft * hard maps (``attention_trace``'s on the modified copy)
+          ``summary`` float64 numpy [nA,H,2]   with "shift", after ONE read-back: per step of the window the mean of latent_shift over
+                                            pairs i != j ([..., 0]) and over i == j ([..., 1]).  A pair counts at step h when ego i is
+                                            present at step start + h and entity j is present in at least one knocked step (column
+                                            ``presence_col`` of the history row non-zero; < 0: everything counts); the environments are
+                                            added in environment order; NaN where nothing counts
+        Environments and jobs are chunked so that what a chunk holds in flight stays under ``max_workspace_mb``; the bits do not depend
+        on the chunking.  numpy in -> numpy out, device tensors in -> device tensors out.  Parameters, gradients, optimiser state,
+        carried state and (with ``deterministic=True``) torch's generator are not touched.  Not covered: knocking the hidden state,
+        the forecast continuation, handing ``latent_ko`` over steps into ``DcntrlMAC.knockout_trace`` as a per-job override (that
+        method's kernel has no such argument), aggregation across data-parallel ranks."""
+        who = "attention_knockout_trace"
+        as_np = isinstance(history, np.ndarray)
+        dev = self.device
+        hist = _as_dev(history, dev)
+        if hist.dim() != 5:
+            raise ValueError(f"{who}: history must be [E,S,nA,N,d], got {tuple(hist.shape)}")
+        E, S, nA, N, d = hist.shape
+        A = self.args.attention_dim
+        if nA != self.n_agents or d != self.obs_shape or not 2 <= N <= ops.L.GAT_MAX_ENTITIES:
+            raise ValueError(f"{who}: history {tuple(hist.shape)} does not fit n_agents={self.n_agents}, obs width {self.obs_shape}, "
+                             f"2 <= N <= {ops.L.GAT_MAX_ENTITIES}")
+        sources, knock, want, tau, jobs, rows = self._knock_spec(who, N, d, sources, want, noise, deterministic, tau, presence_col, entities, baseline)
+        J = len(jobs)
+        ints = (int, np.integer)
+        if not isinstance(start, ints) or not 0 <= start < S:
+            raise ValueError(f"{who}: start={start!r} outside [0, {S})")
+        start = int(start)
+        H = S - start if horizon is None else horizon
+        if not isinstance(H, ints) or not 1 <= H or start + H > S:
+            raise ValueError(f"{who}: horizon={horizon!r} must satisfy 1 <= horizon and start + horizon <= {S}")
+        H = int(H)
+        D = H if duration is None else duration
+        if not isinstance(D, ints) or not 1 <= D <= H:
+            raise ValueError(f"{who}: duration={duration!r} outside [1, horizon={H}]")
+        D = int(D)
+        keep_shift, keep_lat, keep_attn = "shift" in want, "latent_ko" in want, "attention_ko" in want
+        if not (keep_shift or keep_lat or keep_attn):
+            raise ValueError(f"{who}: want={want} asks for nothing")
+        Z = self.args.latent_dim if self.args.GAT_use_behavior else 0
+        if hist.stride(4) != 1 or hist.stride(3) != d:
+            hist = hist.contiguous()
+        src0 = hist.permute(2, 0, 1, 3, 4)                                        # [nA, E, S, N, d] view, read in place
+        lat = self._beh_latent(who, behavior_latent, (E, S, nA, N, Z))
+        if lat is not None:
+            if lat.stride(4) != 1 or lat.stride(3) != Z:
+                lat = lat.contiguous()
+            lat = lat.permute(2, 0, 1, 3, 4)
+        h0 = None
+        if hidden0 is not None:
+            h0 = _as_dev(hidden0, dev)
+            if h0.shape != (E, nA, N, A):
+                raise ValueError(f"{who}: hidden0 {tuple(h0.shape)} != {(E, nA, N, A)}")
+            if h0.stride(3) != 1 or h0.stride(2) != A or h0.data_ptr() % 16 or h0.stride(0) % 4 or h0.stride(1) % 4:
+                h0 = h0.contiguous()
+            h0 = h0.permute(1, 0, 2, 3)
+        if noise is not None:
+            noise = _as_dev(noise, dev)
+            if noise.shape != (nA, E, H, N, N - 1, 2):
+                raise ValueError(f"{who}: noise {tuple(noise.shape)} != {(nA, E, H, N, N - 1, 2)}")
+        # what a chunk holds in flight, in bytes per environment (all agents, the window): the noise and the base walk's latents, and
+        # per (environment, job) the knocked chain's outputs
+        per_env = 4 * nA * H * (2 * N * (N - 1) + N * A)
+        per_job = 4 * nA * H * ((N if keep_shift else 0) + (N * A if keep_lat else 0) + (N * N if keep_attn else 0))
+        budget = int(max_workspace_mb * (1 << 20))
+        if budget < per_env + per_job:
+            raise ValueError(f"{who}: max_workspace_mb={max_workspace_mb} is too small for one environment and one job "
+                             f"({(per_env + per_job) / (1 << 20):.2f} MB)")
+        jc = min(J, (budget - per_env) // per_job)
+        ec = min(E, budget // (per_env + jc * per_job))
+        f32 = dict(dtype=torch.float32, device=dev)
+        res = {"latent": torch.empty(nA, E, H, N, A, **f32)}
+        if keep_shift:
+            res["shift_sq"] = torch.empty(nA, E, J, H, N, **f32)
+        if keep_lat:
+            res["latent_ko"] = torch.empty(nA, E, J, H, N, A, **f32)
+        if keep_attn:
+            res["attention_ko"] = torch.empty(nA, E, J, H, N, N, **f32)
+        for e0 in range(0, E, ec):
+            e1 = min(E, e0 + ec)
+            nz = self._noise(noise, deterministic, nA, e0, e1, (H, N, N - 1, 2), zeros=False)
+            base = res["latent"][:, e0:e1]
+            s0, s1 = src0[:, e0:e1], None if lat is None else lat[:, e0:e1]
+            hc = None if h0 is None else h0[:, e0:e1]
+            ops.gat_trace(self.gat_arena, s0[:, :, start:start + H], None if s1 is None else s1[:, :, start:start + H], hc, nz, tau=tau,
+                          want=("latent",), out={"latent": base})                  # attention_trace's launch and bits
+            for j0 in range(0, J, jc):
+                j1 = min(J, j0 + jc)
+                out = {}
+                if keep_shift:
+                    out["shift_sq"] = res["shift_sq"][:, e0:e1, j0:j1]
+                if keep_lat:
+                    out["latent_ko"] = res["latent_ko"][:, e0:e1, j0:j1]
+                if keep_attn:
+                    out["attn_ko"] = res["attention_ko"][:, e0:e1, j0:j1]
+                ops.gat_knockout_trace(self.gat_arena, s0, s1, hc, jobs[j0:j1], start=start, duration=D, horizon=H,
+                                       base=base if keep_shift else None, noise=nz, tau=tau, knock=knock, baseline=rows, want=tuple(out), out=out)
+        final = {"latent": res["latent"].permute(1, 2, 0, 3, 4)}                   # [nA, E, H, ..] -> [E, H, nA, ..]
+        jn = np.asarray(jobs, dtype=np.int64)
+        if keep_shift:
+            shift = res["shift_sq"].sqrt()                                         # [nA, E, J, H, N]
+            final["latent_shift"] = shift.permute(1, 3, 0, 4, 2)
+        if keep_lat:
+            final["latent_ko"] = res["latent_ko"].permute(1, 3, 0, 2, 4, 5)
+        if keep_attn:
+            final["attention_ko"] = res["attention_ko"].permute(1, 3, 0, 2, 4, 5)
+        if keep_shift:
+            # the two means per agent and step: float64 sums and counts per (agent, env, step) formed where the shifts lie (J N times
+            # fewer numbers to read back than the shifts), ONE host read-back, the environments added on the host
+            win = src0[:, :, start:start + H]
+            present = (win[..., presence_col] != 0) if presence_col >= 0 else torch.ones(nA, E, H, N, dtype=torch.bool, device=dev)
+            jt = torch.as_tensor(jn, device=dev)
+            seen = present[:, :, :D].any(dim=2)[:, :, jt]                              # [nA, E, J]: entity j present in a knocked step
+            own = jt[:, None] == torch.arange(N, device=dev)[None, :]                  # [J, N]: slot j knocks ego i itself
+            count = present[:, :, None] & seen[:, :, :, None, None]                    # [nA, E, J, H, N]
+            parts = []
+            for pick in (~own, own):
+                m = count & pick[None, None, :, None, :]
+                parts += [torch.where(m, shift, 0.0).sum(dim=(2, 4), dtype=torch.float64), m.sum(dim=(2, 4), dtype=torch.float64)]
+            host = torch.stack(parts).cpu().numpy()                                    # [4, nA, E, H]
+            tot = np.zeros((4, nA, H))
+            for e in range(E):                                                         # environment order, whatever the chunks were
+                tot += host[:, :, e]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                summary = np.stack([np.where(tot[c + 1] > 0, tot[c] / tot[c + 1], np.nan) for c in (0, 2)], axis=-1)
+        final = {k: (v.cpu().numpy() if as_np else v) for k, v in final.items()}
+        final["knocked"] = jn
+        final["sources"] = sources
+        final["window"] = (start, D, H)
         if keep_shift:
             final["summary"] = summary
         return final

@@ -300,6 +300,107 @@ def gat_knockout_args(arena, src0, src1, hidden, jobs, base=None, noise=None, ta
     return a, res, keep
 
 
+def _dest_nbjs(out, res, k, lead, inner, dev):
+    """``out[k]`` if the caller gave one, else a fresh tensor: float32 [n_nets, B, J, H, *inner] whose four leading dims may be strided
+    (non-negative); entered into ``res``, checked to lie inside its storage -> (tensor, s_net, s_b, s_job, s_step)"""
+    t = None if out is None else out.get(k)
+    if t is None:
+        t = torch.empty(*lead, *inner, dtype=torch.float32, device=dev)
+    assert t.shape == tuple(lead) + tuple(inner) and t.device == dev and t.dtype == torch.float32, (k, t.shape, t.dtype)
+    expect = 1
+    for d in range(t.dim() - 1, 3, -1):
+        assert t.stride(d) == expect or t.shape[d] == 1, (k, t.shape, t.stride())
+        expect *= t.shape[d]
+    s = t.stride()[:4]
+    assert all(x >= 0 for x in s), (k, s)
+    reach = sum((t.shape[d] - 1) * s[d] for d in range(4)) + expect
+    assert reach <= _room(t), (k, "reaches outside its storage", t.shape, s, _room(t))
+    res[k] = t
+    return (t,) + tuple(s)
+
+
+def gat_knockout_trace(arena, src0, src1, hidden0, jobs, start=0, duration=1, horizon=None, base=None, noise=None, tau=0.01,
+                       knock=(True, True), baseline=(None, None), want=("shift_sq",), out=None, lib=None):
+    """``gat_trace``'s walk run once per job with one entity's input row replaced in the first ``duration`` steps of the window
+    (iplan_gat_knockout_trace), forward only.  src0 [n_nets,B,S,N,d0], src1 [n_nets,B,S,N,d1] or None: the episode fields, views whose
+    first three dims may be strided arbitrarily, read in place; the window is steps start .. start + H - 1 (``horizon`` None: H = S -
+    start).  hidden0 [n_nets,B,N,A] or None (zeros): the state step ``start`` starts from (first two dims strided).  ``jobs``,
+    ``knock``, ``baseline``: as in ``gat_knockout``.  ``noise`` [n_nets,B,H,N,N-1,2] contiguous or None (no gumbel term): the window's
+    samples, the same for every job.  ``want``: which of latent_ko [n_nets,B,J,H,N,A], attn_ko [n_nets,B,J,H,N,N] (entity-indexed soft
+    * hard, diagonal 0), shift_sq [n_nets,B,J,H,N] (sum_c (latent_ko - base)^2; needs ``base`` [n_nets,B,H,N,A], first three dims
+    strided: ``gat_trace``'s latent over the same window, produced by an earlier launch) to produce; ``out``: optional dict of
+    destination views for some of them (the same layouts, first four dims strided).  Everything the kernel will touch is
+    bounds-checked here, on the host.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res, keep = gat_knockout_trace_args(arena, src0, src1, hidden0, jobs, start, duration, horizon, base, noise, tau, knock, baseline, want, out)
+    n_nets, B, _, N, d0 = src0.shape
+    _launch("gat_knockout_trace_kernel", lambda: lib.call("iplan_gat_knockout_trace", a, L.current_stream(src0.device)),
+            work=a.J * a.H * _gat_flops(n_nets, B, N, d0 + a.d1, 32))
+    res["_keep"] = keep
+    return res
+
+
+def gat_knockout_trace_args(arena, src0, src1, hidden0, jobs, start=0, duration=1, horizon=None, base=None, noise=None, tau=0.01,
+                            knock=(True, True), baseline=(None, None), want=("shift_sq",), out=None):
+    """The descriptor of a ``gat_knockout_trace`` launch, its output tensors and what must stay alive until the launch has been
+    queued, checked but not launched: (IplanGatKnockoutTraceArgs, dict, list)."""
+    n_nets, B, S, N, d0 = src0.shape
+    d1 = 0 if src1 is None else src1.shape[-1]
+    A = 32
+    dev = src0.device
+    want = tuple(want)
+    assert want and all(k in GAT_KNOCKOUT_OUTPUTS for k in want), want
+    k0, k1 = bool(knock[0]), bool(knock[1])
+    assert not (k1 and d1 == 0), "source 1 is to be knocked, but there is none"
+    start = int(start)
+    H = S - start if horizon is None else int(horizon)
+    D = int(duration)
+    assert 0 <= start and H >= 1 and start + H <= S and 1 <= D <= H, (start, D, H, S)
+    a = L.GatKnockoutTraceArgs()
+    a.n_nets, a.B, a.N, a.d0, a.d1, a.H, a.D, a.start = n_nets, B, N, d0, d1, H, D, start
+    j_host, j_dev = _job_list(a, jobs, N, dev)
+    J = a.J
+    a.src0 = src0.data_ptr()
+    a.src0_s_net, a.src0_s_b, a.src0_s_step = _nbs_strides(src0, N * d0, "src0")
+    if src1 is not None:
+        assert src1.shape[:4] == (n_nets, B, S, N) and src1.device == dev, src1.shape
+        a.src1 = src1.data_ptr()
+        a.src1_s_net, a.src1_s_b, a.src1_s_step = _nbs_strides(src1, N * d1, "src1")
+    if hidden0 is not None:
+        assert hidden0.shape == (n_nets, B, N, A) and hidden0.device == dev, hidden0.shape
+        a.hidden0 = hidden0.data_ptr()
+        a.h_s_net, a.h_s_b, _ = _nbs_strides(hidden0.unsqueeze(2), N * A, "hidden0")
+    if noise is not None:
+        assert noise.is_contiguous() and noise.shape == (n_nets, B, H, N, N - 1, 2) and noise.dtype == torch.float32 and noise.device == dev, noise.shape
+        a.noise = noise.data_ptr()
+    if base is not None:
+        assert base.shape == (n_nets, B, H, N, A) and base.device == dev, base.shape
+        a.base = base.data_ptr()
+        a.base_s_net, a.base_s_b, a.base_s_step = _nbs_strides(base, N * A, "base")
+    assert "shift_sq" not in want or base is not None, "shift_sq needs base, the latents of the window with nothing knocked"
+    a.knock0, a.knock1 = int(k0), int(k1)
+    keep = [src0, src1, hidden0, noise, base, j_host, j_dev]
+    for which, (row, d) in enumerate(zip(baseline, (d0, d1))):
+        if row is not None:
+            assert row.shape == (d,) and row.dtype == torch.float32 and row.is_contiguous() and row.device == dev, (which, row.shape)
+            setattr(a, f"baseline{which}", row.data_ptr())
+            keep.append(row)
+    a.params = arena.data.data_ptr()
+    a.params_s_net = arena.net_stride
+    for i, k in enumerate(L.GAT_PARAM_ORDER):
+        a.off[i] = arena.off(k)
+    a.tau = tau
+    res = {}
+    pre = {"latent_ko": "lat", "attn_ko": "attn", "shift_sq": "shift"}
+    for k in want:
+        inner = {"latent_ko": (N, A), "attn_ko": (N, N), "shift_sq": (N,)}[k]
+        t, *s = _dest_nbjs(out, res, k, (n_nets, B, J, H), inner, dev)
+        setattr(a, k, t.data_ptr())
+        for name, v in zip(("net", "b", "job", "step"), s):
+            setattr(a, f"{pre[k]}_s_{name}", v)
+    return a, res, keep
+
+
 GAT_SALIENCY_OUTPUTS = ("grad", "pair_gl1", "pair_gxi", "input_grad", "hidden_grad")
 
 
