@@ -1549,6 +1549,39 @@ typedef struct {
 
 int iplan_ac_knockout_trace(const IplanAcKnockoutTraceArgs* args, iplan_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The knock-out chain through time: iplan_ac_knockout_trace with a per-job SOURCE (csrc/policy_knockout_chain.hip).  `kt` describes the
+ * chains, the jobs, the window (H = kt.base.S, D = kt.D) and the outputs exactly as for iplan_ac_knockout_trace.  In addition
+ *   override_src[k]   instead of the row's own vector, job q of step (e, s) of agent `net` reads source k from
+ *                     override_src[k] + q*ov_s_job[k] + net*ov_s_net[k] + e*ov_s_chain[k] + s*ov_s_step[k] + entity*ov_s_ent[k] + column
+ *                     at EVERY step of the window (IplanAcKnockoutArgs' rules: innermost axis contiguous, non-negative strides, read in
+ *                     place).  An overridden source is taken as given: it is not knocked as well, for any job.
+ *   override_base[k]  what column 15 of every tile -- the base chain -- reads for source k instead of the batch's, from
+ *                     override_base[k] + net*ovb_s_net[k] + e*ovb_s_chain[k] + s*ovb_s_step[k] + entity*ovb_s_ent[k] + column;
+ *                     NULL: the batch's own source.  A job of entity -1 reads it too where override_src[k] is NULL.
+ * The other sources selected by kt.knock are replaced for steps s < D only, as iplan_ac_knockout_trace replaces them.  At least one
+ * source must be overridden (without one iplan_ac_knockout_trace is the entry): a job's inputs then differ from the base's at every
+ * step, so
+ *   phase 1 (knocked trunk)  runs over all E x H x ceil(J/15) tiles: iplan_ac_knockout_trace's trunk, the same text, k-tile order and
+ *                    partial sums, with the override pointers in the gather and the entity knock masked off for s >= D
+ *                    -> kt.gi_ko [2 (actor | critic), n_agents, E, H, ceil(J/15), 16, IPLAN_AC_TRACE_GI]
+ *   phase 2 (knocked walk)   IS iplan_ac_knockout_trace's walk kernel, launched with D = H: every column reads its own gi_ko row at
+ *                    every step, column 15 carries the base chain.  kt.base.gi is not read and must be NULL.
+ * kt.base.phases, the outputs and their layout, a*, the exact zeros (a job whose gathered values equal column 15's at every step) and
+ * the independence of a slot's bits from lane, tile, the other jobs, J, H and the outputs asked for: iplan_ac_knockout_trace's.
+ * Refused: what iplan_ac_knockout_trace refuses, an override or base override on an absent source, negative override strides, a base
+ * override without any job override, no override at all, a missing or misaligned gi_ko, kt.base.gi given.
+ */
+typedef struct {
+    IplanAcKnockoutTraceArgs kt;
+    const float* override_src[3];
+    int64_t ov_s_job[3], ov_s_net[3], ov_s_chain[3], ov_s_step[3], ov_s_ent[3];
+    const float* override_base[3];
+    int64_t ovb_s_net[3], ovb_s_chain[3], ovb_s_step[3], ovb_s_ent[3];
+} IplanAcKnockoutChainArgs;
+
+int iplan_ac_knockout_chain(const IplanAcKnockoutChainArgs* args, iplan_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

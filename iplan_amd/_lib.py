@@ -55,7 +55,7 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
                 "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
                 "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout", "iplan_ac_knockout_trace",
-                "iplan_gat_knockout_trace"]
+                "iplan_gat_knockout_trace", "iplan_ac_knockout_chain"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -562,6 +562,14 @@ class AcKnockoutTraceArgs(C.Structure):
     ]
 
 
+class AcKnockoutChainArgs(C.Structure):
+    _fields_ = [
+        ("kt", AcKnockoutTraceArgs), ("override_src", fp * 3),
+        ("ov_s_job", i64 * 3), ("ov_s_net", i64 * 3), ("ov_s_chain", i64 * 3), ("ov_s_step", i64 * 3), ("ov_s_ent", i64 * 3),
+        ("override_base", fp * 3), ("ovb_s_net", i64 * 3), ("ovb_s_chain", i64 * 3), ("ovb_s_step", i64 * 3), ("ovb_s_ent", i64 * 3),
+    ]
+
+
 # ---- FC behaviour ablation -------------------------------------------------------------------------------
 class Mlp3Args(C.Structure):
     _fields_ = [
@@ -603,4 +611,4 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanEncSaliencyArgs": EncSaliencyArgs, "IplanGatSaliencyArgs": GatSaliencyArgs,
                   "IplanPdecSaliencyArgs": PdecSaliencyArgs, "IplanGatKnockoutArgs": GatKnockoutArgs,
                   "IplanAcKnockoutArgs": AcKnockoutArgs, "IplanAcKnockoutTraceArgs": AcKnockoutTraceArgs,
-                  "IplanGatKnockoutTraceArgs": GatKnockoutTraceArgs}
+                  "IplanGatKnockoutTraceArgs": GatKnockoutTraceArgs, "IplanAcKnockoutChainArgs": AcKnockoutChainArgs}

@@ -648,10 +648,12 @@ class DcntrlMAC:
             out = {k: (v if k in keep else v[:, 0]) for k, v in out.items()}
         return {k: (v if k in meta else v.cpu().numpy()) for k, v in out.items()} if as_np else out
 
-    KNOCKOUT_TRACE_WANT = ("kl", "probs_ko", "logp_ko", "values_ko", "h_actor_ko", "h_critic_ko", "summary")
+    KNOCKOUT_TRACE_WANT = ("kl", "probs_ko", "logp_ko", "values_ko", "h_actor_ko", "h_critic_ko", "summary", "latent_shift")
+    SOCIAL_KW = ("sources", "baseline", "noise", "deterministic", "tau", "hidden0")
 
     def knockout_trace(self, batch, entities=None, start=0, duration=1, horizon=None, sources=None, baseline=None, target="recorded",
-                       which="both", hidden0=None, want=("kl",), presence_col=0, max_workspace_mb=256):
+                       which="both", hidden0=None, want=("kl",), presence_col=0, max_workspace_mb=256, override=None, override_base=None,
+                       social=None, social_kw=None):
         """How long does the policy remember a vehicle?  Vehicle j is hidden from the agents for ``duration`` = D steps from step
         ``start`` and then shown again; the nets walk steps start .. start + H - 1 (``horizon`` = H, None: up to the batch's last
         step; ``duration`` None: knocked throughout, D = H) once per entity j of ``entities`` and once with nothing knocked, every
@@ -682,12 +684,46 @@ class DcntrlMAC:
         bits, and so do a shorter ``horizon`` (a prefix), packed or in-place fc1 and any ``want``.  A job whose replaced values equal
         the originals has kl = dlogp = dvalue = state_shift = 0.0 at every step.  Device tensors in -> device tensors out, numpy in ->
         numpy out.  Draws from no generator; parameters, gradient entries, optimiser state, ``hidden_states`` and the batch are not
-        touched.  Not covered: a per-job ``override`` of a source (the chain from ``attention_knockout_trace``'s ``latent_ko``:
-        the kernel has no such argument yet), re-deciding the teacher-forced last action, knocking the state itself, data-parallel aggregation, and
-        layer_N / recurrent_N other than 1."""
+        touched.
+        ``override``: a dict name -> [E, H, nA, J, N, w] over the window (``knockout``'s rules: any strides, innermost contiguous, read
+        in place): job j of step (e, h, a) takes that source from override[e, h, a, j] at EVERY step of the window, not only while
+        h < D; an overridden source is taken as given and not knocked as well.  ``override_base``: a dict name -> [E, H, nA, N, w]: what
+        the BASE chain (and a job -1 without an override of that source) reads instead of the batch's -- it needs an ``override``.
+        With an override one ``iplan_ac_knockout_chain`` launch per chunk runs the knocked trunk over all H steps (the gate workspace
+        is H deep and counted so) and the same walk; a job whose override rows equal ``override_base`` and whose knocked values equal
+        the originals has kl = dlogp = dvalue = state_shift = 0.0 at every step.
+        ``social``: a ``Prediction_policy`` -- the one-call chain "vehicle j out of sight for D steps -> the social context of every
+        ego -> actions and values": per chunk of environments (and of jobs) ``social.attention_knockout_trace`` walks
+        ``history[:, 1:]`` and ``behavior_latent[:, :-1]`` from ``attention_latent[:, start - 1]`` over the GAT window start - 1 ..
+        start - 1 + H with the call's duration and entities; its ``latent_ko`` becomes override["attention_latent"] and its ``latent``
+        (re-walked with nothing knocked, and with the same noise or none) the base override, so that the differences are the knock's
+        alone; both are freed before the next chunk, the knocked latents never exist whole.  The alignment is the rollout's,
+        ``attention_latent[:, t + 1] = GAT(history[:, t + 1], attention_latent[:, t], behavior_latent[:, t])``: GAT row start - 1 + h
+        yields what policy step start + h reads.  It needs ``start >= 1``, ``GAT_enable``, entities in [0, N) and no explicit override
+        of ``attention_latent``.  ``social_kw``: ``sources``, ``baseline``, ``noise`` ([nA, E, H, N, N-1, 2]), ``deterministic``,
+        ``tau`` and ``hidden0`` ([E, nA, N, A]) of the GAT half, as ``attention_knockout_trace`` takes them.  The two halves' workspaces
+        together stay below ``max_workspace_mb``.  With an override the result has ``overridden`` (the names), ``sources`` lists what
+        was knocked in the policy (an overridden source is not among them), and with ``social`` and "latent_shift" in ``want`` the
+        GAT's ``latent_shift`` [E, H, nA, N, J].
+        Not covered: re-deciding the teacher-forced last action, knocking the GRU or GAT state itself, the forecast continuation,
+        data-parallel aggregation, and layer_N / recurrent_N other than 1."""
         a = self.args
         want, ents, srcs, widths = self._knock_request("knockout_trace", want, entities, sources, which, presence_col, max_workspace_mb,
-                                                       baseline=baseline)
+                                                       baseline=baseline, override=override, override_base=override_base)
+        social_kw = {} if social_kw is None else social_kw
+        if not isinstance(social_kw, dict) or any(k not in self.SOCIAL_KW for k in social_kw):
+            raise ValueError(f"knockout_trace: social_kw is a dict whose keys are among {self.SOCIAL_KW}")
+        if social is None and (social_kw or "latent_shift" in want):
+            raise ValueError("knockout_trace: social_kw and want 'latent_shift' need social=")
+        if social is not None:
+            if not a.GAT_enable:
+                raise ValueError("knockout_trace: social= needs GAT_enable: the policy reads no attention_latent")
+            if not isinstance(start, (int, np.integer)) or start < 1:
+                raise ValueError(f"knockout_trace: social= needs start >= 1 (got {start!r}): the GAT step before the window's first is walked")
+            if any(d is not None and d.get("attention_latent") is not None for d in (override, override_base)):
+                raise ValueError("knockout_trace: social= forms the override of attention_latent itself; an explicit one excludes it")
+            if any(j < 0 for j in ents):
+                raise ValueError("knockout_trace: social= takes entities in [0, N): the GAT half has no job -1")
         if isinstance(target, str) and target not in ("recorded", "greedy"):
             raise ValueError(f"knockout_trace: target={target!r}")
         nA, M = self.n_agents, a.rnn_hidden_dim
@@ -730,6 +766,21 @@ class DcntrlMAC:
             full[:, r.sl] = t_in
             tgt = full[:, r.sl]
         base_rows = self._knock_baseline("knockout_trace", baseline, widths, dev)
+        N = a.max_vehicle_num
+        over, over_base = [], []
+        for dst, given, shape, what in ((over, override, (E, H, nA, J, N), "override"), (over_base, override_base, (E, H, nA, N), "override_base")):
+            for k, wd in widths:
+                ov = None if given is None or given.get(k) is None else dev(given[k], th.float32)
+                if ov is not None:
+                    if ov.shape != shape + (wd,):
+                        raise ValueError(f"knockout_trace: {what}[{k!r}] has shape {tuple(ov.shape)}, not {shape + (wd,)}")
+                    if min(ov.stride()) < 0 or (wd > 1 and ov.stride(-1) != 1):
+                        ov = ov.contiguous()
+                dst.append(ov)
+        overridden = tuple(k for (k, _), ov in zip(widths, over) if ov is not None or (social is not None and k == "attention_latent"))
+        if not overridden and any(ov is not None for ov in over_base):
+            raise ValueError("knockout_trace: override_base needs an override: without one the base chain is the batch's")
+        srcs = tuple(k for k in srcs if k not in overridden)
         knock = tuple(k in srcs for k, _ in widths)
         w = {"actor": 0, "critic": 1, "both": 2}[which]
         extra = tuple(k for k in ("probs_ko", "logp_ko", "values_ko") if k in want)
@@ -738,8 +789,25 @@ class DcntrlMAC:
         # chunks: whole environments x a range of jobs; one launch's per-pair outputs and gate workspaces below the budget
         GI = 4 * ops.L.AC_TRACE_GI
         pair_bytes = nA * H * (4 * 5 + 8 + 4 * (("logp_ko" in extra) + ("values_ko" in extra) + a.n_actions * ("probs_ko" in extra)) + 8 * M * bool(want_h))
-        job_bytes = pair_bytes + 2 * nA * D * GI * 16 // 15 + 1
-        env_bytes = 2 * nA * H * GI
+        job_bytes = pair_bytes + 2 * nA * (H if overridden else D) * GI * 16 // 15 + 1         # (an override: the trunk covers all H steps
+        env_bytes = 0 if overridden else 2 * nA * H * GI                                       #  and there is no base gi)
+        gat_env = gat_job = 0
+        if social is not None:
+            # the GAT half of a chunk, as attention_knockout_trace counts it: the noise and the base walk's latents per environment,
+            # latent_ko (and the shifts) per (environment, job)
+            A, g_shift = a.attention_dim, "latent_shift" in want
+            gat_env = 4 * nA * H * (2 * N * (N - 1) + N * A)
+            gat_job = 4 * nA * H * (N * A + (N if g_shift else 0))
+            g_hist = r.field("history", th.float32)[:, 1:]
+            g_beh = r.field("behavior_latent", th.float32)[:, :-1] if social.args.GAT_use_behavior else None
+            g_h0 = social_kw.get("hidden0")
+            g_h0 = r.field("attention_latent", th.float32)[:, start - 1] if g_h0 is None else dev(g_h0, th.float32)
+            g_noise = social_kw.get("noise")
+            g_noise = None if g_noise is None else dev(g_noise, th.float32)
+            g_kw = {k: social_kw[k] for k in ("sources", "baseline", "deterministic", "tau") if k in social_kw}
+            ia = [k for k, _ in widths].index("attention_latent")
+        env_bytes += gat_env
+        job_bytes += gat_job
         budget = int(max_workspace_mb * 2 ** 20)
         Jc = max(1, min(J, (budget - env_bytes) // job_bytes))
         if Jc < J and Jc > 15:
@@ -747,17 +815,35 @@ class DcntrlMAC:
         Ec = max(1, min(E, budget // (env_bytes + job_bytes * Jc)))
 
         def launch(spec, es, js, first):
-            return ops.policy_knockout_trace(self.actor_arena, self.critic_arena, w, spec, es.stop - es.start, H, D, nA, ents[js],
+            ovs = [None if ov is None else ov[es, :, :, js].permute(2, 0, 1, 3, 4, 5) for ov in over]
+            ovb = [None if ov is None else ov[es].permute(2, 0, 1, 3, 4) for ov in over_base]
+            g = None
+            if social is not None:
+                En, Jn = es.stop - es.start, len(ents[js])
+                g = social.attention_knockout_trace(g_hist[es], None if g_beh is None else g_beh[es], hidden0=g_h0[es], entities=ents[js],
+                                                    start=start - 1, duration=D, horizon=H, noise=None if g_noise is None else g_noise[:, es],
+                                                    want=("latent_ko",) + (("shift",) if g_shift else ()), presence_col=presence_col,
+                                                    max_workspace_mb=En * (gat_env + Jn * gat_job) / 2 ** 20, **g_kw)
+                ovs[ia], ovb[ia] = g["latent_ko"].permute(2, 0, 1, 3, 4, 5), g["latent"].permute(2, 0, 1, 3, 4)
+            part = ops.policy_knockout_trace(self.actor_arena, self.critic_arena, w, spec, es.stop - es.start, H, D, nA, ents[js],
                                              hidden0_actor=None if ha is None else ha[es], hidden0_critic=None if hc is None else hc[es],
                                              h_strides=hs, avail=r.avail[es], avail_strides=(r.avail.stride(2), r.avail.stride(1)),
                                              target=None if tgt is None else tgt[es],
                                              target_strides=(0, 0) if tgt is None else (tgt.stride(2), tgt.stride(1)),
                                              n_actions=a.n_actions, knock=knock, baseline=base_rows,
-                                             want=ask + (("base",) if first else ()), packed=r.packed)
+                                             want=ask + (("base",) if first else ()), packed=r.packed, override=ovs, override_base=ovb)
+            if g is not None and g_shift:
+                part["latent_shift"] = g["latent_shift"].permute(2, 0, 1, 4, 3).contiguous()    # [nA, En, H, Jn, N]: scattered as a pair tensor
+            del g, ovs, ovb                                                                     # (freed before the next chunk)
+            return part
 
         out = {"knocked": tuple(ents), "sources": srcs, "window": (start, D, H)}
+        if overridden:
+            out["overridden"] = overridden
         meta = tuple(out)
         self._knock_results(out, self._knock_chunks(r, H, J, Ec, Jc, launch), want)
+        if "latent_shift" in out:
+            out["latent_shift"] = out["latent_shift"].transpose(3, 4)                            # [E, H, nA, N, J], the GAT method's axes
         if "summary" in want:
             filled = dev(batch["filled"]).reshape(-1, T1)[:, r.sl].to(th.float64)                # [E, H]
             pres = self._knock_presence(r.field("history", th.float32)[:, start:start + D], ents, presence_col).any(1)   # in a knocked step

@@ -5,8 +5,8 @@
 //                   action, and what the column gathers (KnockCol); knock_feat is the gather of one k-tile from it
 //   knock_results   what a column forms against column 15 behind the head -- the critic's dvalue, the actor's masked categorical
 //                   (ac_categorical.h), a*, dlogp and knock_kl -- and where it goes
-// The two argument structs (IplanAcKnockoutArgs, IplanAcKnockoutTraceArgs) name the fields read here alike; the functions are templates
-// over them.
+// The argument structs (IplanAcKnockoutArgs, IplanAcKnockoutTraceArgs; IplanAcKnockoutChainArgs through its kt: knock_core) name the
+// fields read here alike; the functions are templates over them.
 #pragma once
 #include <type_traits>
 
@@ -75,18 +75,27 @@ struct KnockTile {
     KnockCol kc;                           // what the column gathers instead
 };
 
+// The struct that carries J, jobs, knock and baseline: the argument struct itself, or the chain's walk description.
+__device__ __forceinline__ const IplanAcKnockoutArgs& knock_core(const IplanAcKnockoutArgs& k) { return k; }
+__device__ __forceinline__ const IplanAcKnockoutTraceArgs& knock_core(const IplanAcKnockoutTraceArgs& k) { return k; }
+__device__ __forceinline__ const IplanAcKnockoutTraceArgs& knock_core(const IplanAcKnockoutChainArgs& k) { return k.kt; }
+
 // tile = r * JT + jt over rows r = ec * steps + sc; n: the lane's column.  The base column gathers the row itself; a job column its own
-// vector of an overridden source (IplanAcKnockoutArgs only) and, of the others, the row with the job's entity replaced where the source
-// is to be knocked.
+// vector of an overridden source (IplanAcKnockoutArgs, IplanAcKnockoutChainArgs) and, of the others, the row with the job's entity
+// replaced where the source is to be knocked.  The chain (IplanAcKnockoutChainArgs) walks every step of the window: its entity knock
+// ends with step D (kt.D), and a source with a base override is read from there by column 15 and by a job of entity -1 that has no
+// vector of its own.
 template <class KA>
 __device__ __forceinline__ KnockTile knock_tile(const KA& ka, const IplanAcFeatures& ft, int64_t tile, int JT, int64_t steps, int net, int n) {
-    constexpr bool has_override = std::is_same<KA, IplanAcKnockoutArgs>::value;
+    constexpr bool is_chain = std::is_same<KA, IplanAcKnockoutChainArgs>::value;
+    constexpr bool has_override = std::is_same<KA, IplanAcKnockoutArgs>::value || is_chain;
+    const auto& kk = knock_core(ka);
     KnockTile t;
     const int64_t r = tile / JT;
     t.jt = (int)(tile - r * JT);
     t.slot = KO_JOBS * t.jt + n;
     t.is_base = n == KO_JOBS;
-    t.valid = t.is_base || t.slot < ka.J;
+    t.valid = t.is_base || t.slot < kk.J;
     t.jobcol = t.valid && !t.is_base;
     t.ec = r / steps; t.sc = r % steps;
     const int64_t pr = t.ec * ft.T_phys + t.sc;
@@ -98,24 +107,37 @@ __device__ __forceinline__ KnockTile knock_tile(const KA& ka, const IplanAcFeatu
         if (ft.last_action) t.last = ft.last_action[(int64_t)net * ft.la_s_net + pr * ft.la_s_row];
         else if (ft.last_action64) t.last = (int)ft.last_action64[(int64_t)net * ft.la64_s_net + pr * ft.la64_s_row];
     }
-    const int job = t.jobcol ? ka.jobs[t.slot] : -1;
-    auto own = [&](int s) -> const float* {                                 // (s is a literal at every call)
+    const int job = t.jobcol ? kk.jobs[t.slot] : -1;
+    auto from_base = [&](int s) {                                            // (s is a literal at every call)
+        if constexpr (is_chain) return t.valid && job < 0 && ka.override_base[s] && ft.w[s] > 0 && !(t.jobcol && ka.override_src[s]);
+        return false;
+    };
+    auto own = [&](int s) -> const float* {
         if constexpr (has_override)
             if (t.jobcol && ka.override_src[s] && ft.w[s] > 0)
                 return ka.override_src[s] + (int64_t)t.slot * ka.ov_s_job[s] + (int64_t)net * ka.ov_s_net[s] + t.ec * ka.ov_s_chain[s] + t.sc * ka.ov_s_step[s];
+        if constexpr (is_chain)
+            if (from_base(s)) return ka.override_base[s] + (int64_t)net * ka.ovb_s_net[s] + t.ec * ka.ovb_s_chain[s] + t.sc * ka.ovb_s_step[s];
         return nullptr;
     };
     auto knocked = [&](int s) {
         if constexpr (has_override)
             if (ka.override_src[s]) return -1;
-        return (ka.knock[s] && ft.w[s] > 0) ? job : -1;
+        if constexpr (is_chain)
+            if (t.sc >= kk.D) return -1;
+        return (kk.knock[s] && ft.w[s] > 0) ? job : -1;
     };
     KnockCol& kc = t.kc;
     kc.ent0 = knocked(0); kc.ent1 = knocked(1); kc.ent2 = knocked(2);
-    kc.bl0 = ka.baseline[0]; kc.bl1 = ka.baseline[1]; kc.bl2 = ka.baseline[2];
+    kc.bl0 = kk.baseline[0]; kc.bl1 = kk.baseline[1]; kc.bl2 = kk.baseline[2];
     kc.ov0 = own(0); kc.ov1 = own(1); kc.ov2 = own(2);
     kc.se0 = kc.se1 = kc.se2 = 0;
     if constexpr (has_override) { kc.se0 = ka.ov_s_ent[0]; kc.se1 = ka.ov_s_ent[1]; kc.se2 = ka.ov_s_ent[2]; }
+    if constexpr (is_chain) {
+        if (from_base(0)) kc.se0 = ka.ovb_s_ent[0];
+        if (from_base(1)) kc.se1 = ka.ovb_s_ent[1];
+        if (from_base(2)) kc.se2 = ka.ovb_s_ent[2];
+    }
     return t;
 }
 

@@ -25,42 +25,16 @@
 // fixed xor butterflies over its four lanes and the reads of column 15, which holds the same bits in every tile.  No atomics, no sums
 // across columns.  A column whose gathered values equal the row's own repeats column 15's arithmetic at every step: its kl, dlogp,
 // dvalue and shift_sq are exactly 0.  A step's results depend on the steps before it only, so a shorter H gives a prefix.
-#include "trace_body.h"
-#include "sal_body.h"
-#include "ac_kmap_ko.h"
+#include "knock_trunk.h"
 
 namespace iplan {
 
-__device__ __forceinline__ int64_t ko_trace_tiles(const IplanAcKnockoutTraceArgs& k) { return (k.J + KO_JOBS - 1) / KO_JOBS; }
-
-// ---- phase 1 -----------------------------------------------------------------------------------------------------------------------
-#define TRUNK_KTILE(T) sal_ktile(sm, T)
-#define TRUNK_FEAT(kt) knock_feat(km, sm, kt, col, net)
-#define TRUNK_GI_ROW ka.gi_ko + ((((((int64_t)which * a.n_agents + net) * a.E + ec) * D + sc) * JT + jt) * 16 + n) * PGI
+// ---- phase 1 (knock_trunk.h: the body, shared with policy_knockout_chain.hip) ---------------------------------------------------------
 __global__ __launch_bounds__(64 * TRUNK_WAVES) void ac_knockout_trace_trunk_kernel(IplanAcKnockoutTraceArgs ka) {
-    const IplanAcTraceArgs& a = ka.base;
-    const int net = (int)blockIdx.y, which = trace_which(a);
-    const IplanAcNet& nw = which ? a.critic : a.actor;
-    const float* __restrict__ P = nw.params + (int64_t)net * nw.params_s_net;
-    const IplanAcFeatures& ft = a.feat;
-    const int l = lane_id(), w = uniform_i(wave_id()), n = l & 15, g = l >> 4;
-    const int D = ka.D, JT = (int)ko_trace_tiles(ka);
-    const int64_t rows = (int64_t)a.E * D;                                   // the knocked rows
-    const int64_t tile = (int64_t)blockIdx.x * TRUNK_WAVES + w;
-    if (tile >= rows * JT) return;                                           // (whole wave; the kernel has no barrier)
-    const KnockTile col = knock_tile(ka, ft, tile, JT, D, net, n);           // (ac_kmap_ko.h; no override)
-    const bool valid = col.valid;
-    const int64_t ec = col.ec, sc = col.sc;
-    const int jt = col.jt;
-    const KMap km = make_kmap(ft);                                           // (kfeat_ko reads the one-hot widths from it)
-    const SalMap sm = sal_make_map(ft);                                      // (the K map as scalars: sal_body.h)
-    const int F = sm.NW + ft.n_actions + ft.n_id, KT = sm.KT;
-
-#include "trace_trunk_impl.h"
+    const IplanAcKnockoutTraceArgs& tk = ka;                                 // (no override)
+    const int steps = ka.D;                                                  // the knocked rows
+#include "knock_trunk_impl.h"
 }
-#undef TRUNK_KTILE
-#undef TRUNK_FEAT
-#undef TRUNK_GI_ROW
 
 // ---- phase 2 -----------------------------------------------------------------------------------------------------------------------
 // sum over the 64 units, ascending, of (col - base)^2: the host's fp32 loop, nothing fused
@@ -148,41 +122,55 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void ac_knockout_trace_walk_kernel
     }
 }
 
-}  // namespace iplan
-
-extern "C" int iplan_ac_knockout_trace(const IplanAcKnockoutTraceArgs* k, iplan_stream_t stream) {
-    using namespace iplan;
-    if (!k) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: null args");
+// The argument checks of iplan_ac_knockout_trace, and of iplan_ac_knockout_chain (`chain`), whose trunk covers all H steps: its gi_ko is
+// H deep and base.gi is not read.
+int ac_knockout_trace_check(const char* who, const IplanAcKnockoutTraceArgs* k, bool chain) {
     const IplanAcTraceArgs* a = &k->base;
-    if (a->E < 1) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: E=%d, at least one chain is needed", a->E);
-    if (a->S < 1) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: H=%d, at least one step is needed", a->S);
-    if (k->D < 1 || k->D > a->S) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: D=%d outside [1, H=%d]", k->D, a->S);
-    if (a->phases < 0 || a->phases > 2) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: phases must be 0, 1 or 2 (got %d)", a->phases);
-    if (const int rc = ac_rows_check("iplan_ac_knockout_trace", "H", a->feat, a->which, a->n_agents, a->S, a->actor, a->critic)) return rc;
-    if (const int rc = ac_jobs_check("iplan_ac_knockout_trace", "H", a->feat, a->E, a->S, k->J, k->jobs, k->jobs_host, k->knock, k->baseline)) return rc;
-    const int64_t JT = (k->J + KO_JOBS - 1) / KO_JOBS;
+    if (a->E < 1) return fail(IPLAN_EINVAL, "%s: E=%d, at least one chain is needed", who, a->E);
+    if (a->S < 1) return fail(IPLAN_EINVAL, "%s: H=%d, at least one step is needed", who, a->S);
+    if (k->D < 1 || k->D > a->S) return fail(IPLAN_EINVAL, "%s: D=%d outside [1, H=%d]", who, k->D, a->S);
+    if (a->phases < 0 || a->phases > 2) return fail(IPLAN_EINVAL, "%s: phases must be 0, 1 or 2 (got %d)", who, a->phases);
+    if (const int rc = ac_rows_check(who, "H", a->feat, a->which, a->n_agents, a->S, a->actor, a->critic)) return rc;
+    if (const int rc = ac_jobs_check(who, "H", a->feat, a->E, a->S, k->J, k->jobs, k->jobs_host, k->knock, k->baseline)) return rc;
     if (a->entropy || a->h_all_actor || a->h_all_critic || a->h_last_actor || a->h_last_critic)
-        return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: of base's outputs only probs, greedy, logp and values (the base chain) are written");
+        return fail(IPLAN_EINVAL, "%s: of base's outputs only probs, greedy, logp and values (the base chain) are written", who);
     bool any = false;
     if (a->which != 1)
         any = any || a->probs || a->greedy || a->logp || k->target_out || k->probs_ko || k->logp_ko || k->greedy_ko || k->kl || k->dlogp ||
               k->shift_sq_actor || k->h_ko_actor || k->logp_all_ko;
     if (a->which != 0) any = any || a->values || k->values_ko || k->dvalue || k->shift_sq_critic || k->h_ko_critic;
-    if (a->phases != 1 && !any) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: no output of the selected nets was asked for");
+    if (a->phases != 1 && !any) return fail(IPLAN_EINVAL, "%s: no output of the selected nets was asked for", who);
     if (!k->gi_ko)
-        return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: the gi_ko workspace [2, n_agents, E, D, ceil(J / 15), 16, %d] is missing", IPLAN_AC_TRACE_GI);
-    if (k->D < a->S && !a->gi)
-        return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: D=%d < H=%d, the echo steps need base.gi as iplan_ac_trace (phases = 1) leaves it", k->D, a->S);
+        return fail(IPLAN_EINVAL, "%s: the gi_ko workspace [2, n_agents, E, %s, ceil(J / 15), 16, %d] is missing", who, chain ? "H" : "D", IPLAN_AC_TRACE_GI);
+    if (chain && a->gi) return fail(IPLAN_EINVAL, "%s: base.gi is given, but it is not read: every step's gi is the column's own gi_ko row", who);
+    if (!chain && k->D < a->S && !a->gi)
+        return fail(IPLAN_EINVAL, "%s: D=%d < H=%d, the echo steps need base.gi as iplan_ac_trace (phases = 1) leaves it", who, k->D, a->S);
     if (!aligned16(k->gi_ko) || !aligned16(a->gi) || !aligned16(k->h_ko_actor) || !aligned16(k->h_ko_critic) || !aligned16(a->packed_actor) ||
         !aligned16(a->packed_critic) || (a->packed_s_net & 3))
-        return fail(IPLAN_EALIGN, "iplan_ac_knockout_trace: gi_ko, base.gi, h_ko and the packed operands must be 16-byte aligned");
-    const unsigned nz = a->which == 2 ? 2u : 1u;
-    const int64_t tiles = (int64_t)a->E * k->D * JT;
+        return fail(IPLAN_EALIGN, "%s: gi_ko, base.gi, h_ko and the packed operands must be 16-byte aligned", who);
+    return IPLAN_OK;
+}
+
+// phase 2 alone.  With k.D = H no step reads base.gi: the chain's walk (policy_knockout_chain.hip)
+int ac_knockout_trace_walk_launch(const IplanAcKnockoutTraceArgs& k, hipStream_t stream) {
+    const IplanAcTraceArgs& a = k.base;
+    hipLaunchKernelGGL(ac_knockout_trace_walk_kernel, dim3((unsigned)((int64_t)a.E * ko_trace_tiles(k)), (unsigned)a.n_agents, a.which == 2 ? 2u : 1u),
+                       dim3(64 * WALK_WAVES), 0, stream, k);
+    return IPLAN_OK;
+}
+
+}  // namespace iplan
+
+extern "C" int iplan_ac_knockout_trace(const IplanAcKnockoutTraceArgs* k, iplan_stream_t stream) {
+    using namespace iplan;
+    if (!k) return fail(IPLAN_EINVAL, "iplan_ac_knockout_trace: null args");
+    if (const int rc = ac_knockout_trace_check("iplan_ac_knockout_trace", k, false)) return rc;
+    const IplanAcTraceArgs* a = &k->base;
+    const int64_t tiles = (int64_t)a->E * k->D * ko_trace_tiles(*k);
     if (a->phases != 2)
-        hipLaunchKernelGGL(ac_knockout_trace_trunk_kernel, dim3((unsigned)((tiles + TRUNK_WAVES - 1) / TRUNK_WAVES), (unsigned)a->n_agents, nz),
+        hipLaunchKernelGGL(ac_knockout_trace_trunk_kernel, dim3((unsigned)((tiles + TRUNK_WAVES - 1) / TRUNK_WAVES), (unsigned)a->n_agents, a->which == 2 ? 2u : 1u),
                            dim3(64 * TRUNK_WAVES), 0, (hipStream_t)stream, *k);
-    if (a->phases != 1)
-        hipLaunchKernelGGL(ac_knockout_trace_walk_kernel, dim3((unsigned)((int64_t)a->E * JT), (unsigned)a->n_agents, nz), dim3(64 * WALK_WAVES), 0,
-                           (hipStream_t)stream, *k);
+    if (a->phases != 1) ac_knockout_trace_walk_launch(*k, (hipStream_t)stream);
     return check_launch("iplan_ac_knockout_trace");
 }
+

@@ -715,8 +715,8 @@ class Prediction_policy:
         Environments and jobs are chunked so that what a chunk holds in flight stays under ``max_workspace_mb``; the bits do not depend
         on the chunking.  numpy in -> numpy out, device tensors in -> device tensors out.  Parameters, gradients, optimiser state,
         carried state and (with ``deterministic=True``) torch's generator are not touched.  Not covered: knocking the hidden state,
-        the forecast continuation, handing ``latent_ko`` over steps into ``DcntrlMAC.knockout_trace`` as a per-job override (that
-        method's kernel has no such argument), aggregation across data-parallel ranks."""
+        the forecast continuation, aggregation across data-parallel ranks.  ``latent_ko`` over steps continues into the policy as
+        ``DcntrlMAC.knockout_trace``'s per-job override; its ``social=`` does both halves in one call."""
         who = "attention_knockout_trace"
         as_np = isinstance(history, np.ndarray)
         dev = self.device

@@ -1077,16 +1077,40 @@ POLICY_KNOCKOUT_TRACE_OUTPUTS = ("base", "kl", "dlogp", "dvalue", "greedy_ko", "
                                  "gi_ko")
 
 
-def policy_knockout_trace_gi_floats(which, n_agents, E, H, D, J):
+def policy_knockout_trace_gi_floats(which, n_agents, E, H, D, J, override=False):
     """floats of the two gi workspaces of one ``policy_knockout_trace`` launch: the rows' base gi [2, nA, E * H, 192] (not needed when
-    D = H) and the knocked columns' gi_ko [2, nA, E, D, ceil(J / 15), 16, 192]"""
+    D = H) and the knocked columns' gi_ko [2, nA, E, D, ceil(J / 15), 16, 192]; with ``override`` (a source has a per-job override) the
+    H-deep gi_ko [2, nA, E, H, ceil(J / 15), 16, 192] alone"""
     JT = (J + POLICY_KNOCKOUT_JOBS_PER_TILE - 1) // POLICY_KNOCKOUT_JOBS_PER_TILE
+    if override:
+        return 2 * n_agents * E * L.AC_TRACE_GI * H * JT * 16
     return 2 * n_agents * E * L.AC_TRACE_GI * ((H if D < H else 0) + D * JT * 16)
+
+
+def _chain_overrides(c, spec, n_agents, E, H, J, dev, override, override_base):
+    """the per-job and base overrides of ``policy_knockout_trace`` into IplanAcKnockoutChainArgs, per source in ``spec.sources`` order:
+    views [nA, E, H, J, N, w] and [nA, E, H, N, w], any non-negative strides with the innermost axis contiguous, bounds-checked"""
+    N = spec.N
+    for k, (_, w, _, _) in enumerate(spec.sources):
+        for ov, shape, what in ((override[k], (n_agents, E, H, J, N, w), "override"), (override_base[k], (n_agents, E, H, N, w), "override_base")):
+            if ov is None:
+                continue
+            assert w > 0, ("source", k, "is absent")
+            assert ov.shape == shape and ov.dtype == torch.float32 and ov.device == dev, (what, k, tuple(ov.shape), shape)
+            st = ov.stride()
+            assert min(st) >= 0 and (st[-1] == 1 or w == 1), (what, k, "negative stride or a strided innermost axis", st)
+            _inside(ov, sum((n - 1) * s for n, s in zip(ov.shape[:-1], st[:-1])) + w, what)
+            if what == "override":
+                c.override_src[k] = ov.data_ptr()
+                c.ov_s_net[k], c.ov_s_chain[k], c.ov_s_step[k], c.ov_s_job[k], c.ov_s_ent[k] = st[:5]
+            else:
+                c.override_base[k] = ov.data_ptr()
+                c.ovb_s_net[k], c.ovb_s_chain[k], c.ovb_s_step[k], c.ovb_s_ent[k] = st[:4]
 
 
 def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_agents, jobs, hidden0_actor=None, hidden0_critic=None,
                           h_strides=(0, 0), avail=None, avail_strides=(0, 0), target=None, target_strides=(0, 0), n_actions=5, knock=None,
-                          baseline=None, want=("kl",), packed=None, out=None, lib=None):
+                          baseline=None, want=("kl",), packed=None, out=None, lib=None, override=None, override_base=None):
     """R_Actor (which=0) / R_Critic (1) / both (2) of every agent walked over the H consecutive steps of E recorded chains once per job,
     every job with its own GRU state from the common ``hidden0_*`` (iplan_ac_knockout_trace; include/iplan_hip.h:
     IplanAcKnockoutTraceArgs), forward only.  In steps 0 .. D-1 the job's entity has its columns of the knocked sources replaced as the
@@ -1098,6 +1122,12 @@ def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_age
     values_ko, probs_ko [.., n_actions], "shift_sq" (shift_sq_actor / shift_sq_critic: the squared L2 distance of the job's state from the
     base chain's after the step), "h_ko" (h_ko_actor / h_ko_critic [.., 64]), "logp_all_ko" ([.., n_actions], the operands of kl; tests) and "gi_ko" (the knocked workspace [2, nA, E, D, ceil(J/15),
     16, 192] as a result; tests); those the selected nets do not provide are left out.  ``out``: optional dict of contiguous destinations.
+    ``override`` / ``override_base``: per source, in the order of ``spec.sources``, views [nA, E, H, J, N, w] / [nA, E, H, N, w] or
+    None -- ``policy_knockout``'s rules (any non-negative strides, innermost axis contiguous, read in place).  Job q reads an overridden
+    source from its own view at EVERY step, not knocked as well; the base chain (and a job -1 without a view of its own) reads
+    ``override_base`` where given, the batch otherwise.  With an override there is no ``iplan_ac_trace`` launch: one
+    ``iplan_ac_knockout_chain`` launch runs the knocked trunk over all H steps (gi_ko is [2, nA, E, H, ceil(J/15), 16, 192]) and the same
+    walk.  A base override needs a per-job override.
     Everything the kernels will read is bounds-checked here, on the host.  Returns a dict of the wanted tensors."""
     lib = _lib(lib)
     want = tuple(want)
@@ -1105,7 +1135,11 @@ def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_age
     M = L.AC_HIDDEN
     assert 1 <= D <= H, (D, H)
     n_src = len(spec.sources)
-    a = L.AcKnockoutTraceArgs()
+    override, override_base = _per_source(override, n_src, "override"), _per_source(override_base, n_src, "override_base")
+    chained = any(ov is not None for ov in override)
+    assert chained or all(ov is None for ov in override_base), "a base override without a per-job override"
+    c = L.AcKnockoutChainArgs() if chained else None
+    a = c.kt if chained else L.AcKnockoutTraceArgs()
     b = a.base
     dev, last_row = _ac_rows(b, actor_arena, critic_arena, which, spec, E, H, n_agents)
     nets = n_agents * (2 if which == 2 else 1)
@@ -1114,7 +1148,7 @@ def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_age
     keep += _job_list(a, jobs, spec.N, dev)
     J = a.J
     JT = (J + POLICY_KNOCKOUT_JOBS_PER_TILE - 1) // POLICY_KNOCKOUT_JOBS_PER_TILE
-    if D < H:
+    if D < H and not chained:
         # the rows' base gi, once per row: the plain trunk over all E x H rows (the D knocked rows' entries are not read)
         ta, _, tkeep = policy_trace_args(actor_arena, critic_arena, which, spec, E, H, n_agents, n_actions=n_actions, want=(), packed=packed)
         ta.phases = 1
@@ -1155,15 +1189,21 @@ def policy_knockout_trace(actor_arena, critic_arena, which, spec, E, H, D, n_age
             setattr(a, "h_ko_" + key, dest("h_ko_" + key, pair + (M,)))
     assert res, ("nothing of", want, "is provided by the selected nets")
     _ac_packed(b, which, packed)
-    gi_shape = (2, n_agents, E, D, JT, 16, L.AC_TRACE_GI)
+    Dg = H if chained else D                                                  # the steps with knocked tiles of their own
+    gi_shape = (2, n_agents, E, Dg, JT, 16, L.AC_TRACE_GI)
     if "gi_ko" in want:
         a.gi_ko = dest("gi_ko", gi_shape)
     else:
-        gi_ko = workspace(dev, 2 * n_agents * E * D * JT * 16 * L.AC_TRACE_GI, "ac_knockout_trace")
+        gi_ko = workspace(dev, 2 * n_agents * E * Dg * JT * 16 * L.AC_TRACE_GI, "ac_knockout_trace")
         a.gi_ko = gi_ko.data_ptr()
         keep.append(gi_ko)
-    _launch("ac_knockout_trace", lambda: lib.call("iplan_ac_knockout_trace", a, stream),
-            work=2.0 * nets * E * JT * 16 * M * (D * (spec.F + 5 * M) + H * 4 * M))
+    work = 2.0 * nets * E * JT * 16 * M * (Dg * (spec.F + 5 * M) + H * 4 * M)
+    if chained:
+        _chain_overrides(c, spec, n_agents, E, H, J, dev, override, override_base)
+        keep += [override, override_base]
+        _launch("ac_knockout_chain", lambda: lib.call("iplan_ac_knockout_chain", c, stream), work=work)
+    else:
+        _launch("ac_knockout_trace", lambda: lib.call("iplan_ac_knockout_trace", a, stream), work=work)
     return res
 
 
