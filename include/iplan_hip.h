@@ -921,6 +921,55 @@ typedef struct {
 int iplan_enc_saliency(const IplanEncSaliencyArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Intent knock-out through time: the finite change of the intent latent when the encoder does not see some steps of the RAW
+ * history, on the chain iplan_enc_saliency differentiates (stated above; no decoder is involved).  With J = T - 1 - L, for every
+ * chain (net, row = e*N + i) and every job q < Q with start s = starts[q] (sorted, distinct, in [0, J)):
+ *   the columns c with bit c of col_mask set, of steps s .. s+D-1, are replaced by baseline[net, c] (0.0 with baseline == NULL) or,
+ *   with hold == 1, by the chain's own x_{s-1, c} (0.0 when s == 0);  the knocked chain starts from the base chain's he_{s-1},
+ *   lat_{s-1} (zeros when s == 0) and walks windows s + h, h < H.  Windows s + h >= J do not exist: their slots are NOT written.
+ * rows = E * N; 1 <= d <= 16, 1 <= Z <= 16; 1 <= L <= IPLAN_ENC_SAL_MAX_L; J >= 1; Q, D, H >= 1; n_nets <= IPLAN_MAX_NETS;
+ * Jn = min(J, starts[Q-1] + H).  Outputs (latent is required, every other one optional):
+ *   latent          [n_nets, rows, Jn, Z]       lat_j of the base chain, the bits iplan_beh_eval's latent has on [0, Jn)
+ *   intent_base     [n_nets, rows, Jn] int32    argmax_z lat_j, lowest index on ties
+ *   latent_ko       [n_nets, rows, Q, H, Z]     the knocked chain's latent after window s + h: the bits iplan_beh_eval gives on an
+ *                                               explicitly modified copy of the history
+ *   hidden_ko       [n_nets, rows, Q, H, 32]    the knocked chain's he after window s + h
+ *   intent          [n_nets, rows, Q, H] int32  argmax_z of latent_ko
+ *   latent_shift_sq [n_nets, rows, Q, H]        sum_z (lat_ko - lat)^2, z ascending, one lane per chain, every difference, product and
+ *   state_shift_sq  [n_nets, rows, Q, H]        sum rounded on its own (the plain fp32 host loop's bits); the same over the 32 units of he
+ * Two kernels: the base walk over windows 0 .. Jn-1 (one wave per 16-chain tile), which records every he_j in `workspace`, then -- when
+ * a per-job output is asked for -- one wave per (tile, job).  The history is read in place through its strides and never copied.
+ * workspace: at least 32 * n_nets * rows * Jn floats, 16-byte aligned.
+ * No atomics, no cross-chain sums: a slot's bits do not depend on its lane, tile, workgroup, on Q or on the other entries of `starts`;
+ * two launches give the same bits; padding lanes of a ragged last tile write nothing; parameters and history are only read.
+ */
+typedef struct {
+    int32_t n_nets, E, N, T, L, d, Z, Q, D, H;
+    const float* hist;          /* x(net,e,t,i,c) = hist[net*h_s_net + e*h_s_e + t*h_s_t + i*d + c]      */
+    int64_t h_s_net, h_s_e, h_s_t;
+    const int32_t* starts;      /* [Q] device memory                                                     */
+    const int32_t* starts_host; /* the same values in host memory (argument checks, Jn)                  */
+    uint32_t col_mask;          /* bit c: column c is replaced; at least one, none at or beyond d        */
+    int32_t hold;               /* 1: the replacement is the chain's own row of step s-1                 */
+    const float* baseline;      /* [n_nets, d] or NULL (zeros); NULL with hold                           */
+    float coef;                 /* soft_update_coef                                                      */
+    const float* enc_params;    /* encoder arena, IPLAN_ENC_* offsets                                    */
+    int64_t enc_s_net;
+    int64_t enc_off[IPLAN_ENC_NPARAM];
+    float* workspace;
+    int64_t workspace_floats;
+    float* latent;
+    int32_t* intent_base;
+    float* latent_ko;
+    float* hidden_ko;
+    int32_t* intent;
+    float* latent_shift_sq;
+    float* state_shift_sq;
+} IplanEncKnockoutArgs;
+
+int iplan_enc_knockout(const IplanEncKnockoutArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Attention inspection: GAT_Net.forward walked over S >= 1 consecutive steps in one launch, forward only,
  *   h_s = GAT([src0_s || src1_s], h_{s-1}),   s = 0 .. S-1,   h_{-1} = hidden0 (NULL: zeros),
  * one workgroup per (net, env) scene; a step's arithmetic is the inference form of iplan_gat_fwd (nothing saved), so the

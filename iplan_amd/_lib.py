@@ -55,7 +55,7 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
                 "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
                 "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout", "iplan_ac_knockout_trace",
-                "iplan_gat_knockout_trace", "iplan_ac_knockout_chain"]
+                "iplan_gat_knockout_trace", "iplan_ac_knockout_chain", "iplan_enc_knockout"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -426,6 +426,18 @@ class EncSaliencyArgs(C.Structure):
     ]
 
 
+class EncKnockoutArgs(C.Structure):
+    _fields_ = [
+        ("n_nets", i32), ("E", i32), ("N", i32), ("T", i32), ("L", i32), ("d", i32), ("Z", i32), ("Q", i32), ("D", i32), ("H", i32),
+        ("hist", fp), ("h_s_net", i64), ("h_s_e", i64), ("h_s_t", i64),
+        ("starts", fp), ("starts_host", fp), ("col_mask", C.c_uint32), ("hold", i32), ("baseline", fp), ("coef", C.c_float),
+        ("enc_params", fp), ("enc_s_net", i64), ("enc_off", i64 * len(ENC_PARAM_ORDER)),
+        ("workspace", fp), ("workspace_floats", i64),
+        ("latent", fp), ("intent_base", fp), ("latent_ko", fp), ("hidden_ko", fp), ("intent", fp),
+        ("latent_shift_sq", fp), ("state_shift_sq", fp),
+    ]
+
+
 GAT_TRACE_NSTAT = 6      # IPLAN_GAT_TRACE_NSTAT
 
 
@@ -611,4 +623,5 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanEncSaliencyArgs": EncSaliencyArgs, "IplanGatSaliencyArgs": GatSaliencyArgs,
                   "IplanPdecSaliencyArgs": PdecSaliencyArgs, "IplanGatKnockoutArgs": GatKnockoutArgs,
                   "IplanAcKnockoutArgs": AcKnockoutArgs, "IplanAcKnockoutTraceArgs": AcKnockoutTraceArgs,
-                  "IplanGatKnockoutTraceArgs": GatKnockoutTraceArgs, "IplanAcKnockoutChainArgs": AcKnockoutChainArgs}
+                  "IplanGatKnockoutTraceArgs": GatKnockoutTraceArgs, "IplanAcKnockoutChainArgs": AcKnockoutChainArgs,
+                  "IplanEncKnockoutArgs": EncKnockoutArgs}

@@ -34,6 +34,9 @@ class Behavior_policy(_SoftBehaviorPolicy):
     def latent_saliency(self, *args, **kwargs):
         raise NotImplementedError("latent_saliency() is implemented for the soft-update Behavior_policy only, not the fully-connected ablation")
 
+    def latent_knockout(self, *args, **kwargs):
+        raise NotImplementedError("latent_knockout() is implemented for the soft-update Behavior_policy only, not the fully-connected ablation")
+
     def init_behavior_net(self):
         """nova/behavior_FC_policy.py:55-76."""
         a = self.args

@@ -28,6 +28,9 @@ class Behavior_policy(_SoftBehaviorPolicy):
     def latent_saliency(self, *args, **kwargs):
         raise NotImplementedError("latent_saliency() is implemented for the soft-update Behavior_policy only, not the hard-update ablation")
 
+    def latent_knockout(self, *args, **kwargs):
+        raise NotImplementedError("latent_knockout() is implemented for the soft-update Behavior_policy only, not the hard-update ablation")
+
     def latent_update(self, history, encoder_hidden, prev_latent, out_latent=None, out_hidden=None):
         """nova/behavior_policy.py:78-115: new latent = softmax(encoder(history)), prev_latent is ignored."""
         as_np = isinstance(history, np.ndarray)

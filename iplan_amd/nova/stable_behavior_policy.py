@@ -540,6 +540,196 @@ class Behavior_policy:
             out_np[k] = piece.astype({torch.float32: np.float32, torch.int64: np.int64, torch.bool: np.bool_}.get(res[k].dtype, np.float64))
         return out_np
 
+    def latent_knockout(self, history, starts, duration=1, horizon=None, columns=None, baseline=None, want=("shift",), presence_col=0,
+                        max_workspace_mb=256):
+        """How far a vehicle's intent moves, whether its argmax intent changes, and for how many windows the encoder remembers, when
+        the encoder does not see some steps (or some columns) of the RAW history: the finite counterpart of ``latent_saliency``, on
+        the chain ``latent_trace`` walks (csrc/enc_knockout.hip; no decoder is run).  history [E, T, nA, N, d] as for ``latent_trace``
+        (numpy in -> numpy out, device tensor in -> device tensors out); L = max_history_len, J = T - 1 - L.
+          starts    an int or a sorted sequence of distinct ints in [0, J); Q = their number, one job per entry
+          duration  D >= 1: job q with start s replaces, for every vehicle chain at once (a vehicle's rows feed only its own latent),
+                    the selected columns of steps s .. s+D-1; steps that no reported window reads are harmless
+          columns   None = all d, or a sequence of distinct ints in [0, d)
+          baseline  None = zeros (the observation wrapper's encoding of an unseen vehicle), a float row [d] or [nA, d], or "hold" =
+                    the vehicle's own row of step s-1 (zeros when s = 0)
+          horizon   H >= 1, None = J - min(starts): job q reports windows s_q + h, h < H.  Entries with s_q + h >= J do not exist:
+                    they are exactly 0 / False and marked in window_valid
+          want      any of "shift", "latent_ko", "hidden_ko" (only adds)
+        The knocked chain starts from the base chain's he_{s-1}, lat_{s-1}.  Windows s .. s+D+L-2 read a replaced row; later ones
+        differ only through the carried state and the averaged latent.  Returns a dict, pair axes [E, H, nA, Q, N]:
+          latent        [E, Jn, nA, N, Z]  the base chain, Jn = min(J, max(starts) + H): bit for bit a prefix of ``latent_trace``'s
+          intent_base   [E, Jn, nA, N] int64  its argmax (lowest index on ties)
+          latent_shift, state_shift   || lat_ko - lat ||_2 and || he_ko - he ||_2 at the same window
+          intent, flip  int64 argmax of the knocked latent; intent != intent_base at the same window
+          latent_ko [.., Z], hidden_ko [.., 32]   the knocked chain itself ("latent_ko" / "hidden_ko"): latent_ko of job q is what
+                        ``latent_trace`` returns at windows s_q .. on an explicitly modified copy
+          starts [Q] int64, window = (D, H), direct_windows = min(H, D + L - 1), window_valid [Q, H] bool, columns [.] int64
+          echo_shift, echo_flip_rate [nA, Q, H] float64 ("shift"): the mean of latent_shift / flip over the (env, vehicle) pairs of
+                        valid windows whose vehicle is present (history[e, t, a, n, presence_col] != 0) in at least one knocked step
+                        t < T -- every pair with presence_col=None; 0 where nothing counts
+        Envs (and, where one env does not fit, jobs) are processed in chunks so that workspace plus the chunk's outputs stay under
+        ``max_workspace_mb``; chunked and unchunked calls give the same bits.  Deterministic; draws from no generator; no parameter,
+        gradient, optimiser or carried state is touched; a data-parallel ``dp`` attachment is not consulted."""
+        self.join_decoder()
+        as_np = isinstance(history, np.ndarray)
+        if not as_np and not torch.is_tensor(history):
+            raise ValueError("latent_knockout: history must be a numpy array or a tensor [E, T, nA, N, d]")
+        if history.ndim != 5:
+            raise ValueError(f"latent_knockout: history must be [E, T, nA, N, d], got {tuple(history.shape)}")
+        E, T, nA, N, d = (int(s) for s in history.shape)
+        Lw, Z, dev = self.max_history_len, self.latent_dim, self.device
+        J = T - 1 - Lw
+        if nA != self.n_agents or d != self.args.obs_shape_single or E < 1 or N < 1:
+            raise ValueError(f"latent_knockout: history {tuple(history.shape)} does not fit n_agents={self.n_agents}, d={self.args.obs_shape_single}")
+        if J < 1:
+            raise ValueError(f"latent_knockout: T={T} leaves no window (J = T - 1 - L = {J})")
+        if Lw > ops.L.ENC_SAL_MAX_L:
+            raise NotImplementedError(f"latent_knockout: max_history_len={Lw} > {ops.L.ENC_SAL_MAX_L} is not supported by iplan_enc_knockout")
+
+        def as_int(v, what):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"latent_knockout: {what} must be an int, got {v!r}")
+            return int(v)
+
+        def int_list(v, what):
+            if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)):
+                return [int(v)]
+            if isinstance(v, (str, bytes)):
+                raise ValueError(f"latent_knockout: {what} must be an int or a sequence of ints, got {v!r}")
+            try:
+                return [as_int(j, f"an entry of {what}") for j in list(v)]
+            except TypeError:
+                raise ValueError(f"latent_knockout: {what} must be an int or a sequence of ints, got {v!r}") from None
+        st = int_list(starts, "starts")
+        if not st or any(s < 0 or s >= J for s in st) or any(b <= a for a, b in zip(st, st[1:])):
+            raise ValueError(f"latent_knockout: starts must be sorted, distinct and inside [0, J={J}), got {st}")
+        Q = len(st)
+        D = as_int(duration, "duration")
+        if D < 1:
+            raise ValueError(f"latent_knockout: duration={D} must be at least 1")
+        H = J - st[0] if horizon is None else as_int(horizon, "horizon")
+        if H < 1:
+            raise ValueError(f"latent_knockout: horizon={H} must be at least 1")
+        if columns is None:
+            cols = list(range(d))
+        else:
+            if isinstance(columns, (int, np.integer)):
+                raise ValueError(f"latent_knockout: columns must be None or a sequence of ints, got {columns!r}")
+            cols = int_list(columns, "columns")
+            if not cols or any(c < 0 or c >= d for c in cols) or len(set(cols)) != len(cols):
+                raise ValueError(f"latent_knockout: columns must be distinct and inside [0, d={d}), got {cols}")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if any(k not in ("shift", "latent_ko", "hidden_ko") for k in want):
+            raise ValueError(f"latent_knockout: want={want} -- known: 'shift', 'latent_ko', 'hidden_ko'")
+        if presence_col is not None and not 0 <= as_int(presence_col, "presence_col") < d:
+            raise ValueError(f"latent_knockout: presence_col={presence_col} outside [0, d={d})")
+        hold, base_row = False, None
+        if isinstance(baseline, str):
+            if baseline != "hold":
+                raise ValueError(f"latent_knockout: baseline={baseline!r} -- None, 'hold', or a float row [d] or [nA, d]")
+            hold = True
+        elif baseline is not None:
+            try:
+                b = torch.as_tensor(baseline)
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError(f"latent_knockout: baseline={baseline!r} -- None, 'hold', or a float row [d] or [nA, d]") from None
+            if not b.dtype.is_floating_point or tuple(b.shape) not in ((d,), (nA, d)):
+                raise ValueError(f"latent_knockout: a baseline row must be float [d] or [nA, d] = {(nA, d)}, got {b.dtype} {tuple(b.shape)}")
+            base_row = b.to(device=dev, dtype=torch.float32).expand(nA, d).contiguous()
+        if isinstance(max_workspace_mb, (bool, np.bool_)) or not (isinstance(max_workspace_mb, (int, float)) and max_workspace_mb > 0):
+            raise ValueError(f"latent_knockout: max_workspace_mb={max_workspace_mb!r} must be positive")
+
+        h = _as_dev(history, dev)
+        hist = h.permute(2, 0, 1, 3, 4)                                            # [nA, E, T, N, d] view, read in place
+        if hist.stride(4) != 1 or hist.stride(3) != d:
+            hist = hist.contiguous()
+        Jn = ops.enc_knockout_windows(J, st, H)
+        names = ["latent", "intent_base", "intent", "latent_shift_sq", "state_shift_sq"]
+        names += [k for k in ("latent_ko", "hidden_ko") if k in want]
+        tail = dict(intent=(), latent_shift_sq=(), state_shift_sq=(), latent_ko=(Z,), hidden_ko=(32,))
+        # chunks: envs first; where ONE env with all jobs does not fit, groups of jobs as well (each group walks the base chain as far
+        # as it needs).  Counted against the limit: the kernel's workspace (he_j of windows 0 .. Jn-1), the base chain's outputs and
+        # the chunk's per-job outputs.
+        limit = int(max_workspace_mb * 2 ** 20) // 4
+        slot = nA * N * H * sum(int(np.prod(tail[k])) for k in names[2:])           # output floats per env and job
+        base_env = nA * N * Jn * (32 + Z + 1)                                       # workspace and base outputs per env
+        per_env = base_env + Q * slot
+        if per_env <= limit:
+            Ec, groups = min(E, limit // per_env), [(0, Q)]
+        else:
+            Ec, g = 1, (limit - base_env) // slot
+            if g < 1:
+                raise ValueError(f"latent_knockout: max_workspace_mb={max_workspace_mb} is too small for one env and one job "
+                                 f"({4 * (base_env + slot)} bytes)")
+            groups = [(q, min(Q, q + g)) for q in range(0, Q, g)]
+        f32, i32 = torch.float32, torch.int32
+        full = {k: torch.zeros((nA, E, N, Q, H) + tail[k], dtype=i32 if k == "intent" else f32, device=dev) for k in names[2:]}
+        full["latent"] = torch.empty(nA, E, N, Jn, Z, dtype=f32, device=dev)
+        full["intent_base"] = torch.empty(nA, E, N, Jn, dtype=i32, device=dev)
+        for e0 in range(0, E, Ec):
+            e1 = min(E, e0 + Ec)
+            for q0, q1 in groups:
+                last = q1 == Q                                                       # the group that walks all Jn base windows
+                out = ops.enc_knockout(self.enc_arena, hist[:, e0:e1], st[q0:q1], D, H, Lw, Z, self.soft_update_coef, columns=cols,
+                                       baseline=base_row, hold=hold, want=names if last else names[2:])
+                for k in names[2:]:
+                    full[k][:, e0:e1, :, q0:q1] = out[k].reshape((nA, e1 - e0, N, q1 - q0, H) + tail[k])
+                if last:
+                    full["latent"][:, e0:e1] = out["latent"].reshape(nA, e1 - e0, N, Jn, Z)
+                    full["intent_base"][:, e0:e1] = out["intent_base"].reshape(nA, e1 - e0, N, Jn)
+        sq = torch.tensor(st, device=dev)
+        win = sq[:, None] + torch.arange(H, device=dev)[None, :]                                   # [Q, H]: the window of every slot
+        window_valid = win < J
+        pair = lambda t: t.permute(*((1, 4, 0, 3, 2) + tuple(range(5, t.dim()))))                  # [nA, E, N, Q, H, ..] -> [E, H, nA, Q, N, ..]
+        intent_base = full["intent_base"].to(torch.int64)
+        intent = full["intent"].to(torch.int64)
+        flip = (intent != intent_base[..., win.clamp(max=Jn - 1)]) & window_valid
+        res = {"latent": full["latent"].permute(1, 3, 0, 2, 4), "intent_base": intent_base.permute(1, 3, 0, 2),
+               "latent_shift": pair(torch.sqrt(full["latent_shift_sq"])), "state_shift": pair(torch.sqrt(full["state_shift_sq"])),
+               "intent": pair(intent), "flip": pair(flip)}
+        for k in ("latent_ko", "hidden_ko"):
+            if k in want:
+                res[k] = pair(full[k])
+        res["starts"], res["window_valid"], res["columns"] = sq, window_valid, torch.tensor(cols, device=dev)
+        if "shift" in want:
+            # the pairs that count: the vehicle is present in at least one knocked step t < T (a difference of running counts)
+            if presence_col is None:
+                counted = torch.ones(nA, E, Q, N, dtype=torch.bool, device=dev)
+            else:
+                seen = (hist[..., presence_col] != 0).to(torch.int64).cumsum(dim=2)                # [nA, E, T, N]
+                seen = torch.cat([torch.zeros_like(seen[:, :, :1]), seen], dim=2)
+                counted = (seen[:, :, (sq + D).clamp(max=T)] - seen[:, :, sq]) > 0                 # [nA, E, Q, N]
+            counted = counted[:, :, :, None, :] & window_valid[None, None, :, :, None]             # [nA, E, Q, H, N]
+            shift64 = res["latent_shift"].permute(2, 0, 3, 1, 4).double()                          # [nA, E, Q, H, N]
+            flip64 = res["flip"].permute(2, 0, 3, 1, 4).double()
+            # float64 sums in a fixed order: environments ascending, then vehicles ascending
+            num = torch.zeros(2, nA, Q, H, N, dtype=torch.float64, device=dev)
+            cnt = torch.zeros(nA, Q, H, N, dtype=torch.float64, device=dev)
+            for e in range(E):
+                w = counted[:, e].double()
+                num = num + torch.stack([shift64[:, e] * w, flip64[:, e] * w])
+                cnt = cnt + w
+            tot, ctot = num[..., 0], cnt[..., 0]
+            for i in range(1, N):
+                tot, ctot = tot + num[..., i], ctot + cnt[..., i]
+            mean = torch.where(ctot > 0, tot / ctot.clamp(min=1.0), torch.zeros_like(tot))
+            res["echo_shift"], res["echo_flip_rate"] = mean[0], mean[1]
+        meta = {"window": (D, H), "direct_windows": min(H, D + Lw - 1)}
+        if not as_np:
+            res.update(meta)
+            return res
+        # numpy callers: ONE read-back (every piece is exactly representable in float64)
+        keys = list(res)
+        host = torch.cat([res[k].reshape(-1).double() for k in keys]).cpu().numpy()
+        out_np, at = {}, 0
+        for k in keys:
+            n = res[k].numel()
+            piece = host[at:at + n].reshape(tuple(res[k].shape))
+            at += n
+            out_np[k] = piece.astype({torch.float32: np.float32, torch.int64: np.int64, torch.bool: np.bool_}.get(res[k].dtype, np.float64))
+        out_np.update(meta)
+        return out_np
+
     # ---------------------------------------------------------------------------- checkpoints
     def save_models(self, path):
         self.join_decoder()

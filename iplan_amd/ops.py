@@ -2208,6 +2208,89 @@ def enc_saliency(enc_arena, hist, windows, K, L_win, Z, coef, seed=None, seed_in
     return res
 
 
+def enc_knockout_windows(J, starts, H):
+    """Jn: the windows 0 .. Jn-1 of the base chain that ``iplan_enc_knockout`` walks for these jobs"""
+    return min(J, max(starts) + H)
+
+
+def enc_knockout_workspace_floats(n_nets, rows, J, starts, H):
+    """floats of caller workspace ``iplan_enc_knockout`` needs: he_j of the base chain's windows 0 .. Jn-1"""
+    return n_nets * rows * enc_knockout_windows(J, starts, H) * 32
+
+
+ENC_KO_OUTPUTS = ("latent", "intent_base", "latent_ko", "hidden_ko", "intent", "latent_shift_sq", "state_shift_sq")
+
+
+def enc_knockout(enc_arena, hist, starts, D, H, L_win, Z, coef, columns=None, baseline=None, hold=False,
+                 want=("latent", "intent_base", "intent", "latent_shift_sq", "state_shift_sq"), out=None, workspace=None, lib=None):
+    """The finite change of the intent latent when the selected ``columns`` (None = all d) of steps s .. s+D-1 of the raw history are
+    replaced, for every start s in ``starts`` (sorted, distinct ints in [0, J), J = T - 1 - L_win), every net and every (env, entity)
+    chain, over the H windows s .. s+H-1 (csrc/enc_knockout.hip).  hist [n_nets, E, T, N, d] (first three dims may be strided) is read
+    in place.  The replacement: ``baseline`` [n_nets, d] (None = zeros) or, with ``hold=True``, the chain's own row of step s-1.
+    ``want``: names out of ENC_KO_OUTPUTS ("latent" is always produced).  Returns a dict with latent [n_nets, E*N, Jn, Z] and
+    intent_base int32 [n_nets, E*N, Jn] of the base chain (Jn = min(J, max(starts) + H)), latent_ko [n_nets, E*N, Q, H, Z], hidden_ko
+    [n_nets, E*N, Q, H, 32], intent int32 [n_nets, E*N, Q, H], latent_shift_sq / state_shift_sq [n_nets, E*N, Q, H]; None for what
+    was not asked for.  Slots of windows s + h >= J are zero.  ``out``: optional dict of destination tensors of exactly those shapes
+    (contiguous) -- the kernel writes only the slots that exist, so the caller prepares the others; ``workspace``: an optional
+    float32 tensor of at least enc_knockout_workspace_floats(...) elements."""
+    lib = _lib(lib)
+    n_nets, E, T, N, d = hist.shape
+    assert hist.dtype == torch.float32 and hist.stride(4) == 1 and hist.stride(3) == d
+    want = tuple(dict.fromkeys(("latent",) + tuple(want)))
+    assert all(k in ENC_KO_OUTPUTS for k in want), want
+    dev = hist.device
+    starts = [int(s) for s in starts]
+    Q, rows, J = len(starts), E * N, T - 1 - L_win
+    ok = Q > 0 and J >= 1 and H >= 1 and all(0 <= s < J for s in starts)          # (everything else is refused by the entry point)
+    Jn = enc_knockout_windows(J, starts, H) if ok else 0
+    a = L.EncKnockoutArgs()
+    a.n_nets, a.E, a.N, a.T, a.L, a.d, a.Z, a.Q, a.D, a.H = n_nets, E, N, T, L_win, d, Z, Q, D, H
+    a.hist, a.h_s_net, a.h_s_e, a.h_s_t = hist.data_ptr(), hist.stride(0), hist.stride(1), hist.stride(2)
+    # the kernel reads steps 0 .. Jn-1 of every (net, env): they must lie inside the history's storage
+    if ok and min(hist.stride(0), hist.stride(1), hist.stride(2)) >= 0:
+        _inside(hist, (n_nets - 1) * hist.stride(0) + (E - 1) * hist.stride(1) + (Jn - 1) * hist.stride(2) + N * d, "enc_knockout: hist")
+    s_host = (C.c_int32 * max(Q, 1))(*starts)
+    s_dev = torch.tensor(starts, dtype=torch.int32, device=dev) if Q else None
+    a.starts, a.starts_host = L.ptr(s_dev), C.cast(s_host, C.c_void_p)
+    cols = list(range(d)) if columns is None else [int(c) for c in columns]
+    assert all(0 <= c < 32 for c in cols), cols
+    a.col_mask = sum(1 << c for c in set(cols))
+    a.hold = int(hold)
+    if baseline is not None:
+        assert baseline.dtype == torch.float32 and baseline.device == dev and baseline.is_contiguous() and baseline.shape == (n_nets, d), baseline.shape
+        a.baseline = baseline.data_ptr()
+    a.coef = coef
+    a.enc_params, a.enc_s_net = enc_arena.data.data_ptr(), enc_arena.net_stride
+    for i, k in enumerate(L.ENC_PARAM_ORDER):
+        a.enc_off[i] = enc_arena.off(k)
+    floats = n_nets * rows * Jn * 32
+    if workspace is None:
+        workspace = torch.empty(max(floats, 4), dtype=torch.float32, device=dev)   # (an inspection call: not kept between calls)
+    else:
+        assert workspace.dtype == torch.float32 and workspace.device == dev and workspace.is_contiguous() and workspace.numel() >= floats
+    a.workspace, a.workspace_floats = workspace.data_ptr(), floats
+    Hs = max(H, 0)
+    shapes = dict(latent=(Jn, Z), intent_base=(Jn,), latent_ko=(Q, Hs, Z), hidden_ko=(Q, Hs, 32), intent=(Q, Hs), latent_shift_sq=(Q, Hs),
+                  state_shift_sq=(Q, Hs))
+    res = {k: None for k in ENC_KO_OUTPUTS}
+    for k in want:
+        shape = (n_nets, rows) + shapes[k]
+        dt = torch.int32 if k in ("intent_base", "intent") else torch.float32
+        if out is not None and k in out:
+            t = out[k]
+            assert t.shape == shape and t.dtype == dt and t.is_contiguous() and t.device == dev, (k, t.shape, shape)
+        elif k in ("latent", "intent_base"):
+            t = torch.empty(shape, dtype=dt, device=dev)
+        else:
+            t = torch.zeros(shape, dtype=dt, device=dev)                            # slots of windows past J stay zero
+        res[k] = t
+        setattr(a, k, t.data_ptr())
+    _launch("enc_knockout_kernel", lambda: lib.call("iplan_enc_knockout", a, L.current_stream(dev)))
+    res["_args"] = a
+    res["_keep"] = (hist, s_host, s_dev, baseline, workspace)
+    return res
+
+
 def beh_backward(enc_arena, dec_arena, fwd, accumulate=False, penalty=0.0, E_norm=0, defer_dec_wgrad=False, lib=None):
     """BPTT of beh_forward's behaviour loss: fills both gradient arenas (``accumulate=True``: adds to them -- launches on
     disjoint env chunks of one batch, normalised by a shared ``win_norm``).

@@ -79,6 +79,11 @@ def shares_queue(a, b, device):
             torch.cuda.synchronize(device)
         ms = max(e0.elapsed_time(e1), 1e-3)
         st["cycles"] = int(min(max(1_000_000 * 0.5 / ms, 100_000), 50_000_000))     # ~0.5 ms
+    # a stream's FIRST submission sets its hardware queue up, which can take longer than the spin: on a pool stream that was never used
+    # the op below then finishes late and reads as "shares" once, and not again.  Both streams get one op of their own first.
+    for s in (a, b):
+        with torch.cuda.stream(s):
+            st["flag"].add_(0.0)
     torch.cuda.synchronize(device)
     a0, a1, b1 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
     with torch.cuda.stream(a):

@@ -238,6 +238,57 @@ if "behavior_evaluate" in set(sys.argv[1:]):
     print(f"Behavior_policy.evaluate ({E} envs, no optional outputs): median {ev[len(ev) // 2]:.3f} ms  min {ev[0]:.3f}  max {ev[-1]:.3f}  "
           f"peak extra device memory {peak_extra(lambda: pol.evaluate(batch)) / 2 ** 20:.1f} MiB", flush=True)
 
+if "latent_knockout" in set(sys.argv[1:]):
+    # intent knock-out through time (iplan_enc_knockout through Behavior_policy.latent_knockout) against the route without it: one
+    # latent_trace of the episode and one per occlusion interval on an explicitly modified copy, the differences and means in torch,
+    # one read-back.  Q = 8 starts spread over the episode, D = 5, H = 20, want=("shift",); the two alternate in one process, a pair
+    # of events around each call; median of 20 after 3 warm-up rounds.
+    pol = loop.behavior
+    k_hist = batch["history"][:, :-1].float().contiguous()                          # [E, T, nA, N, d]
+    Lw = args.max_history_len
+    T = k_hist.shape[1]
+    J = T - 1 - Lw
+    Qk, Dk, Hk = 8, 5, 20
+    k_starts = sorted({round(i * (J - Hk) / (Qk - 1)) for i in range(Qk)})
+
+    def run_knockout():
+        r = pol.latent_knockout(k_hist, k_starts, duration=Dk, horizon=Hk, want=("shift",))
+        return torch.stack([r["echo_shift"], r["echo_flip_rate"]]).cpu()
+
+    def run_by_hand():
+        base = pol.latent_trace(k_hist)                                                     # [E, J, nA, N, Z]
+        rows = []
+        for s in k_starts:
+            c = k_hist.clone()
+            c[:, s:s + Dk] = 0.0
+            ko = pol.latent_trace(c)[:, s:s + Hk]
+            ref = base[:, s:s + Hk]
+            shift = (ko - ref).square().sum(-1).sqrt().double()                             # [E, H, nA, N]
+            flip = (ko.argmax(-1) != ref.argmax(-1)).double()
+            seen = (k_hist[:, s:s + Dk, :, :, 0] != 0).any(dim=1)[:, None].double()         # [E, 1, nA, N]
+            cnt = seen.sum(dim=(0, 3)).clamp(min=1.0)                                       # [1, nA]
+            rows.append(torch.stack([(shift * seen).sum(dim=(0, 3)) / cnt, (flip * seen).sum(dim=(0, 3)) / cnt]))
+        return torch.stack(rows).cpu()
+
+    a_new, a_old = run_knockout(), run_by_hand()                                            # [2, nA, Q, H] and [Q, 2, H, nA]
+    print("largest difference of the two routes' echo_shift:", float((a_new[0] - a_old[:, 0].permute(2, 0, 1)).abs().max()), flush=True)
+    times = {"latent_knockout": [], "latent_trace x (1 + Q) + torch": []}
+    for rnd in range(23):
+        for name, fn in (("latent_knockout", run_knockout), ("latent_trace x (1 + Q) + torch", run_by_hand)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd >= 3:
+                times[name].append(e0.elapsed_time(e1))
+    Jn = min(J, max(k_starts) + Hk)
+    print(f"shape: {nA} nets x {E} envs x {N} entities, T = {T}, L = {Lw}, starts = {k_starts}, D = {Dk}, H = {Hk}; "
+          f"workspace {4 * nA * E * N * Jn * 32 / 2 ** 20:.1f} MiB (he_j of {Jn} windows)", flush=True)
+    for name, t in times.items():
+        t = sorted(t)
+        print(f"{name:32s} median {t[len(t) // 2]:.3f} ms  min {t[0]:.3f}  max {t[-1]:.3f}  ({len(t)} rounds after 3 warm-up rounds)", flush=True)
+
 if "gat_phases12" in set(sys.argv[1:]):           # libraries built with -DGAT_P3_CLOCKS only
     clk = torch.zeros(nA * E, 12, dtype=torch.int64, device=dev)
     ops.gat_forward(loop.prediction.gat_arena, hist, lat, hid, noise, out=out, phase_clocks=clk)
