@@ -96,22 +96,22 @@ extern "C" int iplan_ac_pack_fc1(const IplanAcPackArgs* a, iplan_stream_t stream
 }
 
 // argument checks of iplan_ac_fwd, shared with the fused rollout launch (gat.hip: iplan_gat_enc_ac_fwd)
-__attribute__((visibility("hidden"))) int iplan::ac_fwd_check(const IplanAcFwdArgs* a) {
-    if (!a) return fail(IPLAN_EINVAL, "iplan_ac_fwd: null args");
-    if (a->ksplit != 1 && a->ksplit != 8) return fail(IPLAN_EINVAL, "iplan_ac_fwd: ksplit must be 1 or 8 (got %d)", a->ksplit);
+__attribute__((visibility("hidden"))) int iplan::ac_fwd_check(const IplanAcFwdArgs* a, const char* what) {
+    if (!a) return fail(IPLAN_EINVAL, "%s: null args", what);
+    if (a->ksplit != 1 && a->ksplit != 8) return fail(IPLAN_EINVAL, "%s: ksplit must be 1 or 8 (got %d)", what, a->ksplit);
     if (a->which < 0 || a->which > 2 || a->n_agents < 1 || a->rows < 1)
-        return fail(IPLAN_EINVAL, "iplan_ac_fwd: bad which/n_agents/rows");
-    if (a->feat.T < 1 || a->feat.T_phys < a->feat.T) return fail(IPLAN_EINVAL, "iplan_ac_fwd: bad T/T_phys");
+        return fail(IPLAN_EINVAL, "%s: bad which/n_agents/rows", what);
+    if (a->feat.T < 1 || a->feat.T_phys < a->feat.T) return fail(IPLAN_EINVAL, "%s: bad T/T_phys", what);
     if (a->which != 1 && (a->actor.n_out < 1 || a->actor.n_out > 16))
-        return fail(IPLAN_EINVAL, "iplan_ac_fwd: n_actions=%d outside [1,16]", a->actor.n_out);
-    if (a->which != 1 && a->mode == 1 && !a->q_noise) return fail(IPLAN_EINVAL, "iplan_ac_fwd: mode 1 needs q_noise");
-    if (a->which != 1 && a->mode == 2 && !a->actions_in) return fail(IPLAN_EINVAL, "iplan_ac_fwd: mode 2 needs actions_in");
+        return fail(IPLAN_EINVAL, "%s: n_actions=%d outside [1,16]", what, a->actor.n_out);
+    if (a->which != 1 && a->mode == 1 && !a->q_noise) return fail(IPLAN_EINVAL, "%s: mode 1 needs q_noise", what);
+    if (a->which != 1 && a->mode == 2 && !a->actions_in) return fail(IPLAN_EINVAL, "%s: mode 2 needs actions_in", what);
     if (a->fc1_pre && (a->ksplit != 1 || a->ln_stats_mode != 2 || !a->ln_stats || !iplan::aligned16(a->fc1_pre)))
-        return fail(IPLAN_EINVAL, "iplan_ac_fwd: fc1_pre needs ksplit 1 and stored LayerNorm statistics (ln_stats_mode 2)");
+        return fail(IPLAN_EINVAL, "%s: fc1_pre needs ksplit 1 and stored LayerNorm statistics (ln_stats_mode 2)", what);
     if (a->ksplit_wg > 1 && (a->ksplit != 8 || a->ln_stats_mode != 0 || !a->ks_scratch || !a->ks_count || a->saved ||
                              (a->which != 1 && !a->packed_actor) || (a->which != 0 && !a->packed_critic) || a->ksplit_wg > 8))
-        return fail(IPLAN_EINVAL, "iplan_ac_fwd: ksplit_wg needs the rollout shape (ksplit 8, folded LayerNorm statistics, packed fc1 operands incl. "
-                                  "W gamma / W beta, no saved activations), ks_scratch and ks_count");
+        return fail(IPLAN_EINVAL, "%s: ksplit_wg needs the rollout shape (ksplit 8, folded LayerNorm statistics, packed fc1 operands incl. "
+                                  "W gamma / W beta, no saved activations), ks_scratch and ks_count", what);
     return IPLAN_OK;
 }
 

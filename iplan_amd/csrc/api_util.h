@@ -25,7 +25,7 @@ inline int check_launch(const char* what) {
     return IPLAN_OK;
 }
 
-int ac_fwd_check(const IplanAcFwdArgs* a);   // argument checks of iplan_ac_fwd (actor_critic.hip), also used by iplan_gat_enc_ac_fwd
+int ac_fwd_check(const IplanAcFwdArgs* a, const char* what = "iplan_ac_fwd");   // argument checks of iplan_ac_fwd (actor_critic.hip), also used by iplan_gat_enc_ac_fwd: ``what`` names the refusing entry point
 
 // The checks the policy inspection entries share (api.cpp); `who`: the entry's name as its messages begin, `steps`: its name for S.
 // Rows, features and nets: which / n_agents, N, feat.T = S <= T_phys, the widths, the sources, n_out and the parameters of the selected

@@ -109,7 +109,7 @@ extern "C" int iplan_gat_enc_ac_fwd(const IplanGatFwdArgs* a, const IplanEncFwdA
         return fail(IPLAN_EINVAL, "iplan_gat_enc_ac_fwd: unsupported encoder dims d=%d Z=%d L=%d", e->d, e->Z, e->L);
     if (!e->x || !e->h0 || !e->hL || !e->latent_out || !e->params)
         return fail(IPLAN_EINVAL, "iplan_gat_enc_ac_fwd: null encoder tensor pointer");
-    if (int rc = ac_fwd_check(c)) return rc;
+    if (int rc = ac_fwd_check(c, "iplan_gat_enc_ac_fwd")) return rc;
     if (c->ksplit != 8 || c->saved || c->fc1_pre || c->ln_stats_mode != 0)
         return fail(IPLAN_EINVAL, "iplan_gat_enc_ac_fwd: the actor/critic part must be a rollout-shaped launch (ksplit 8, one-pass "
                                   "LayerNorm statistics, nothing saved)");

@@ -10,6 +10,7 @@ Fiber* g_cur = nullptr;
 
 static constexpr size_t kStack = 192 * 1024;
 static std::vector<std::unique_ptr<char[]>> g_stacks;
+static unsigned long long g_blocks_launched = 0;   // workgroups of every launch so far (iplan_emu_blocks_launched: the tests' view of a grid)
 
 float* dyn_lds() {
     static std::vector<float> buf(40960 + 64);
@@ -57,6 +58,7 @@ static void trampoline() {
 
 void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
     const int nthreads = (int)(block.x * block.y * block.z);
+    g_blocks_launched += (unsigned long long)grid.x * grid.y * grid.z;
     while ((int)g_stacks.size() < nthreads) g_stacks.emplace_back(new char[kStack]);
     for (unsigned bz = 0; bz < grid.z; ++bz)
         for (unsigned by = 0; by < grid.y; ++by)
@@ -109,4 +111,8 @@ void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
             }
 }
 
+unsigned long long blocks_launched() { return g_blocks_launched; }
+
 }  // namespace iplan_emu
+
+extern "C" unsigned long long iplan_emu_blocks_launched() { return iplan_emu::blocks_launched(); }
