@@ -16,39 +16,24 @@
 //     Without the sums neither next_t nor the mask is read.
 // The sums are reduced in a fixed order (per-tile partials, then one wave per (net, window, step, sum) over the tiles): no
 // floating-point atomics, two launches on the same inputs give the same bits.
-#include "api_util.h"
-#include "gru_tile.h"
+// The encoder's half -- its LDS block, staging, row fetch, step, head with the soft update, the tile -> chain mapping and the look-ahead
+// index -- is enc_chain.h's, which enc_knockout.hip walks too.
+#include "enc_chain.h"
 
 namespace iplan {
 
 constexpr int VD = 64, VDT = 4, VDLD = VD + 8;     // decoder_rnn_dim; LDS leading dims: ld % 16 == 8 -> conflict-free fragment reads
-constexpr int VE = 32, VET = 2, VELD = VE + 8;     // encoder_rnn_dim
-constexpr int VLLD = 24;                           // leading dim of the two input Linears (<= 16 real columns)
+constexpr int VLLD = 24;                           // leading dim of the decoder's input Linear (<= 16 real columns)
 constexpr int V_DWIH = 0;
 constexpr int V_DWHH = V_DWIH + 3 * VD * VDLD;
 constexpr int V_DOUT = V_DWHH + 3 * VD * VDLD;
 constexpr int V_DLIN = V_DOUT + 16 * VDLD;
-constexpr int V_EWIH = V_DLIN + VD * VLLD;
-constexpr int V_EWHH = V_EWIH + 3 * VE * VELD;
-constexpr int V_EOUT = V_EWHH + 3 * VE * VELD;
-constexpr int V_ELIN = V_EOUT + 16 * VELD;
-constexpr int V_DB = V_ELIN + VE * VLLD;           // decoder biases: linear 0 (64) | b_ih 64 (192) | b_hh 256 (192) | out 448 (16)
-constexpr int V_EB = V_DB + VD + 6 * VD + 16;      // encoder biases: linear 0 (32) | b_ih 32 (96) | b_hh 128 (96) | out 224 (16)
-constexpr int V_LDS_FLOATS = V_EB + VE + 6 * VE + 16;
+constexpr int V_EWIH = V_DLIN + VD * VLLD;         // the encoder's weights part (enc_chain.h: W_ih first)
+constexpr int V_DB = V_EWIH + EC_W_FLOATS;         // decoder biases: linear 0 (64) | b_ih 64 (192) | b_hh 256 (192) | out 448 (16)
+constexpr int V_EB = V_DB + VD + 6 * VD + 16;      // the encoder's bias part
+constexpr int V_LDS_FLOATS = V_EB + EC_B_FLOATS;
 static_assert(V_LDS_FLOATS * sizeof(float) <= 160 * 1024, "the weights of both nets must fit one CU's LDS");
 static_assert(V_DB % 4 == 0 && V_EB % 4 == 0 && V_DLIN % 4 == 0 && V_EWIH % 4 == 0, "16-byte aligned fragments");
-
-// entries 4g .. 4g+3 of a d-wide row of any alignment: four dword loads from addresses clamped to the row, NOT masked (the
-// consumer masks them: the loads of the next step stay in flight under this step's arithmetic)
-__device__ __forceinline__ f32x4 beh_eval_row(const float* __restrict__ row, int d, int g) {
-    const IPLAN_GLOBAL_AS float* p = as_global(row);
-    f32x4 v;
-    for (int q = 0; q < 4; ++q) {
-        const int i = 4 * g + q;
-        v[q] = p[i < d ? i : d - 1];
-    }
-    return v;
-}
 
 // The latent (columns 0 .. Z-1 of a D-layout tile) moved to columns d .. d+Z-1, zero elsewhere: the decoder's input tile is
 // [x (d) | latent (Z)].  Column c of the result is column c - d of the source: register (c - d) & 3 -- the same on every lane for a
@@ -85,52 +70,40 @@ __global__ __launch_bounds__(256) void beh_eval_kernel(IplanBehEvalArgs a) {
         stage_matrix(lds + V_DWHH, VDLD, 3 * VD, PD + a.dec_off[IPLAN_DEC_WHH], 3 * VD, VD);
         stage_matrix(lds + V_DOUT, VDLD, 16, PD + a.dec_off[IPLAN_DEC_OUT_W], a.d, VD);
         stage_matrix(lds + V_DLIN, VLLD, VD, PD + a.dec_off[IPLAN_DEC_LIN_W], VD, a.d + a.Z);
-        stage_matrix(lds + V_EWIH, VELD, 3 * VE, PE + a.enc_off[IPLAN_ENC_WIH], 3 * VE, VE);
-        stage_matrix(lds + V_EWHH, VELD, 3 * VE, PE + a.enc_off[IPLAN_ENC_WHH], 3 * VE, VE);
-        stage_matrix(lds + V_EOUT, VELD, 16, PE + a.enc_off[IPLAN_ENC_OUT_W], a.Z, VE);
-        stage_matrix(lds + V_ELIN, VLLD, VE, PE + a.enc_off[IPLAN_ENC_LIN_W], VE, a.d);
+        enc_chain_stage_w(lds + V_EWIH, PE, a.enc_off, a.d, a.Z);
         stage_vector(lds + V_DB, VD, PD + a.dec_off[IPLAN_DEC_LIN_B], VD);
         stage_vector(lds + V_DB + 64, 3 * VD, PD + a.dec_off[IPLAN_DEC_BIH], 3 * VD);
         stage_vector(lds + V_DB + 256, 3 * VD, PD + a.dec_off[IPLAN_DEC_BHH], 3 * VD);
         stage_vector(lds + V_DB + 448, 16, PD + a.dec_off[IPLAN_DEC_OUT_B], a.d);
-        stage_vector(lds + V_EB, VE, PE + a.enc_off[IPLAN_ENC_LIN_B], VE);
-        stage_vector(lds + V_EB + 32, 3 * VE, PE + a.enc_off[IPLAN_ENC_BIH], 3 * VE);
-        stage_vector(lds + V_EB + 128, 3 * VE, PE + a.enc_off[IPLAN_ENC_BHH], 3 * VE);
-        stage_vector(lds + V_EB + 224, 16, PE + a.enc_off[IPLAN_ENC_OUT_B], a.Z);
+        enc_chain_stage_b(lds + V_EB, PE, a.enc_off, a.Z);
     }
     __syncthreads();
     const float* s_dwih = lds + V_DWIH;
     const float* s_dwhh = lds + V_DWHH;
     const float* s_dout = lds + V_DOUT;
     const float* s_dlin = lds + V_DLIN;
-    const float* s_ewih = lds + V_EWIH;
-    const float* s_ewhh = lds + V_EWHH;
-    const float* s_eout = lds + V_EOUT;
-    const float* s_elin = lds + V_ELIN;
+    const float* s_ew = lds + V_EWIH;
     const float* s_db = lds + V_DB;
     const float* s_eb = lds + V_EB;
 
     const int l = lane_id(), n = l & 15, g = l >> 4;
-    const int rows = a.E * a.N;
-    const int tiles = (rows + 15) / 16;
+    const int tiles = (a.E * a.N + 15) / 16;
     const int tile = (int)blockIdx.x * 4 + wave_id();
     if (tile >= tiles) return;
-    const int row = tile * 16 + n;
-    const bool valid = row < rows;
-    const int rc = valid ? row : 0;                       // padding lanes of a ragged last tile walk row 0 and write nothing
-    const int e = rc / a.N, ent = rc - e * a.N;
+    const EncChain c = enc_chain_of(a, net, tile, n);
+    const bool valid = c.valid;
     const int L = a.L, d = a.d, Z = a.Z, J = a.T - 1 - L;
-    const float* __restrict__ hrow = a.hist + (int64_t)net * a.h_s_net + (int64_t)e * a.h_s_e + (int64_t)ent * d;
-    const float* __restrict__ mrow = SUMS ? a.mask + ((int64_t)net * a.E + e) * a.T : nullptr;
-    const int64_t gr = (int64_t)net * rows + rc;
+    const float* __restrict__ hrow = c.hrow;
+    const float* __restrict__ mrow = SUMS ? a.mask + ((int64_t)net * a.E + c.e) * a.T : nullptr;
+    const int64_t gr = c.gr;
 
-    f32x4 hd[VDT], he[VET], lat = splat4(0.f);
+    f32x4 hd[VDT], he[ECT], lat = splat4(0.f);
     for (int t = 0; t < VDT; ++t) hd[t] = splat4(0.f);
-    for (int t = 0; t < VET; ++t) he[t] = splat4(0.f);
+    for (int t = 0; t < ECT; ++t) he[t] = splat4(0.f);
 
     // curr_t, next_t and the mask entry of the step AFTER the current one are requested before the current step's arithmetic;
     // a step index below 0 (the zero padding of the first windows) fetches step 0 and is masked where it is consumed
-    auto fetch = [&](int st) { return beh_eval_row(hrow + (int64_t)(st < 0 ? 0 : st) * a.h_s_t, d, g); };
+    auto fetch = [&](int st) { return enc_chain_row(hrow + (int64_t)(st < 0 ? 0 : st) * a.h_s_t, d, g); };
     f32x4 x_raw = fetch(1 - L), y_raw = splat4(0.f);
     float m_raw = 0.f;
     if (SUMS) {
@@ -148,19 +121,13 @@ __global__ __launch_bounds__(256) void beh_eval_kernel(IplanBehEvalArgs a) {
             }
             const f32x4 tg = y_raw;
             const float m = m_raw;
-            {
-                const bool last_t = t + 1 == L, more = j + 1 < J;
-                const int jn = last_t && more ? j + 1 : j, tn = last_t ? (more ? 0 : t) : t + 1;
-                x_raw = fetch(jn - (L - 1) + tn);
-                if (SUMS) {
-                    y_raw = fetch(jn + 1 + tn);
-                    m_raw = mrow[jn + 1 + tn];
-                }
+            const EncNext nx = enc_chain_next(j, t, L, j, J);
+            x_raw = fetch(nx.j - (L - 1) + nx.t);
+            if (SUMS) {
+                y_raw = fetch(nx.j + 1 + nx.t);
+                m_raw = mrow[nx.j + 1 + nx.t];
             }
-            // encoder step
-            f32x4 ue[VET];
-            for (int T = 0; T < VET; ++T) ue[T] = relu4(dense_tile<1>(s_elin, VLLD, 16 * T, x, bfrag_lds(s_eb, T)));
-            gru_step_lds<VET, VET>(s_ewih, VELD, s_ewhh, VELD, s_eb + 32, s_eb + 128, ue, he, nullptr);
+            enc_chain_step(s_ew, s_eb, x, he);
             // decoder step
             f32x4 ud[VDT];
             for (int T = 0; T < VDT; ++T) ud[T] = relu4(dense_tile<1>(s_dlin, VLLD, 16 * T, xin, bfrag_lds(s_db, T)));
@@ -190,21 +157,8 @@ __global__ __launch_bounds__(256) void beh_eval_kernel(IplanBehEvalArgs a) {
                 if (l < 2) a.part[((((int64_t)net * J + j) * L + t) * 2 + l) * tiles + tile] = l == 0 ? s0 : s1;
             }
         }
-        // latent head + soft update (stable_behavior_policy.py:223-230), as beh_enc_fwd_kernel does it
-        const f32x4 lg = dense_tile<VET>(s_eout, VELD, 0, he, bfrag_lds(s_eb + 224, 0));
-        float mx = -INFINITY;
-        for (int q = 0; q < 4; ++q)
-            if (4 * g + q < Z) mx = fmaxf(mx, lg[q]);
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        f32x4 ex;
-        float ss = 0.f;
-        for (int q = 0; q < 4; ++q) {
-            ex[q] = (4 * g + q < Z) ? expf(lg[q] - mx) : 0.f;
-            ss += ex[q];
-        }
-        ss = group_sum(ss);
-        for (int q = 0; q < 4; ++q) lat[q] = (1.0f - a.coef) * lat[q] + (ex[q] / ss) * a.coef;
+        // latent head + soft update (stable_behavior_policy.py:223-230)
+        enc_chain_latent(s_ew, s_eb, he, lat, Z, g, a.coef);
         if (a.latent) {
             float* lrow = a.latent + (gr * J + j) * Z;
             for (int q = 0; q < 4; ++q)

@@ -1,7 +1,5 @@
 // Intent saliency: d <v, lat_j> / d x_{j-r}, the derivative of the intent latent with respect to the RAW history, by BPTT through the
-// behaviour encoder's chain (the one behavior_eval.hip walks; Linear -> ReLU -> GRU32 -> Linear -> softmax -> soft update, no decoder):
-//    he_{-1} = 0, lat_{-1} = 0;  window j:  h = he_{j-1};  t < L:  s = j-L+1+t, x~ = x_s (0 where s < 0), u = ReLU(W_lin x~ + b), h = GRU32(u, h)
-//    he_j = h,  p_j = softmax(W_out he_j + b_out),  lat_j = (1 - c) lat_{j-1} + c p_j
+// behaviour encoder's chain (enc_chain.h states it: Linear -> ReLU -> GRU32 -> Linear -> softmax p_j -> soft update, no decoder).
 // Against beh_enc_bwd_kernel (behavior_learn.hip), which forms PARAMETER gradients from 688 recorded floats per chain-step: this one
 // differentiates with respect to the INPUT and records nothing but he_j (32 floats per chain-window).  Two passes:
 //   1. enc_sal_fwd_kernel: one wave per 16-chain tile walks windows 0 .. max(windows), keeps he_j in scratch and, at the target
@@ -13,37 +11,26 @@
 //      A step is read by up to L windows; windows are walked downwards, so step s is complete once window w = s has been walked:
 //      at most L rows are pending at a time (a ring in LDS), and a finished row is reduced to its outputs and written once.
 // The chain's steps in both directions, the weights in LDS and the lane-private slab (here: the entering states and the ring) are
-// chain_sal.h's, shared with pdec_saliency.hip; the number of waves per workgroup follows from L.  No atomics, no cross-chain sums: the
-// MFMA keeps chains in separate columns, so a slot's bits do not depend on its lane, tile, workgroup or on the other target windows.
+// chain_sal.h's, shared with pdec_saliency.hip; the number of waves per workgroup follows from L.  The head p_j, the argmax and the
+// tile -> chain mapping are enc_chain.h's, shared with behavior_eval.hip and enc_knockout.hip.  No atomics, no cross-chain
+// sums: the MFMA keeps chains in separate columns, so a slot's bits do not depend on its lane, tile, workgroup or on the other windows.
 #include "chain_sal.h"
+#include "enc_chain.h"
 
 namespace iplan {
 
 static_assert(chain_fits(IPLAN_ENC_SAL_MAX_L), "one wave's slab and ring must fit beside the weights");
 static_assert(!chain_fits(IPLAN_ENC_SAL_MAX_L + 1), "IPLAN_ENC_SAL_MAX_L is what the LDS budget admits");
+static_assert(CH == EC && CHT == ECT, "chain_sal.h's state tiles are enc_chain.h's");
 
 // columns 4g .. 4g+3 of step `st` of a chain's history, zero past column d and for the zero padding st < 0
 __device__ __forceinline__ f32x4 enc_sal_x(const float* __restrict__ hrow, int64_t s_t, int st, int d, int g) {
     return chain_row_load(hrow + (int64_t)(st < 0 ? 0 : st) * s_t, st >= 0, d, g);
 }
 
-// p = softmax(W_out h + b_out) over the Z real columns (0 elsewhere), as beh_eval_kernel forms it
+// p = softmax(W_out h + b_out) on chain_sal.h's layout
 __device__ __forceinline__ f32x4 enc_sal_softmax(const float* lds, const f32x4 (&h)[CHT], int Z, int g) {
-    const f32x4 lg = dense_tile<CHT>(lds + C_OUT, CHLD, 0, h, bfrag_lds(lds + C_BOUT, 0));
-    float mx = -INFINITY;
-    for (int q = 0; q < 4; ++q)
-        if (4 * g + q < Z) mx = fmaxf(mx, lg[q]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    f32x4 ex;
-    float ss = 0.f;
-    for (int q = 0; q < 4; ++q) {
-        ex[q] = (4 * g + q < Z) ? expf(lg[q] - mx) : 0.f;
-        ss += ex[q];
-    }
-    ss = group_sum(ss);
-    for (int q = 0; q < 4; ++q) ex[q] = ex[q] / ss;
-    return ex;
+    return enc_chain_softmax(lds + C_OUT, CHLD, lds + C_BOUT, h, Z, g);
 }
 
 // d <gv, p> / d logits = p (gv - <p, gv>).  Every product and the difference are rounded on their own (no contraction into an fma):
@@ -75,13 +62,11 @@ __global__ __launch_bounds__(256) void enc_sal_fwd_kernel(IplanEncSaliencyArgs a
     const int tiles = (rows + 15) / 16;
     const int tile = uniform_i((int)blockIdx.x * 4 + wave_id());
     if (tile >= tiles) return;
-    const int row = tile * 16 + n;
-    const bool valid = row < rows;
-    const int rc = valid ? row : 0;                       // padding lanes of a ragged last tile walk row 0 and write nothing
-    const int e = rc / a.N, ent = rc - e * a.N;
+    const EncChain c = enc_chain_of(a, net, tile, n);
+    const bool valid = c.valid;
     const int L = a.L, d = a.d, Z = a.Z, nW = a.nW;
-    const float* __restrict__ hrow = a.hist + (int64_t)net * a.h_s_net + (int64_t)e * a.h_s_e + (int64_t)ent * d;
-    const int64_t gr = (int64_t)net * rows + rc;
+    const float* __restrict__ hrow = c.hrow;
+    const int64_t gr = c.gr;
     float* __restrict__ he_all = a.scratch;
     int32_t* __restrict__ tix = reinterpret_cast<int32_t*>(a.scratch + (int64_t)a.n_nets * rows * Jn * CH);
 
@@ -94,6 +79,8 @@ __global__ __launch_bounds__(256) void enc_sal_fwd_kernel(IplanEncSaliencyArgs a
             chain_step(lds, enc_sal_x(hrow, a.h_s_t, j - (L - 1) + t, d, g), u, h, nullptr);
         }
         for (int T = 0; T < CHT; ++T) vstore_a(he_all + (gr * Jn + j) * CH, valid, T, h[T]);
+        // (the soft update in place, on a finished p: handed to a helper, the compiler contracts the other product into the fma and
+        // lat_j changes in its last bit -- profiles/r29 notes)
         const f32x4 p = enc_sal_softmax(lds, h, Z, g);
         for (int q = 0; q < 4; ++q) lat[q] = (1.0f - a.coef) * lat[q] + p[q] * a.coef;
         if (wi < nW && a.windows[wi] == j) {
@@ -103,16 +90,7 @@ __global__ __launch_bounds__(256) void enc_sal_fwd_kernel(IplanEncSaliencyArgs a
                     if (valid && 4 * g + q < Z) lrow[4 * g + q] = lat[q];
             }
             if (!a.seed) {
-                // argmax over the Z components, lowest index on ties: within the lane, then across the chain's four lane groups
-                float bv = -INFINITY;
-                int bi = 16;
-                for (int q = 0; q < 4; ++q)
-                    if (4 * g + q < Z && lat[q] > bv) { bv = lat[q]; bi = 4 * g + q; }
-                for (int m = 16; m <= 32; m <<= 1) {
-                    const float ov = __shfl_xor(bv, m);
-                    const int oi = __shfl_xor(bi, m);
-                    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-                }
+                const int bi = enc_chain_argmax(lat, Z, g);
                 const int pick = a.seed_index >= 0 ? a.seed_index : bi;
                 if (valid && g == 0) {
                     tix[gr * nW + wi] = pick;
@@ -137,12 +115,10 @@ __global__ __launch_bounds__(256) void enc_sal_bwd_kernel(IplanEncSaliencyArgs a
     const int task = uniform_i((int)blockIdx.x * wpb + wave_id());
     if (task >= tiles * nW) return;
     const int tile = task / nW, wi = task - tile * nW;
-    const int row = tile * 16 + n;
-    const bool valid = row < rows;
-    const int rc = valid ? row : 0;
-    const int e = rc / a.N, ent = rc - e * a.N;
-    const float* __restrict__ hrow = a.hist + (int64_t)net * a.h_s_net + (int64_t)e * a.h_s_e + (int64_t)ent * d;
-    const int64_t gr = (int64_t)net * rows + rc;
+    const EncChain c = enc_chain_of(a, net, tile, n);
+    const bool valid = c.valid;
+    const float* __restrict__ hrow = c.hrow;
+    const int64_t gr = c.gr;
     const int64_t slot = gr * nW + wi;
     const float* __restrict__ he_all = a.scratch;
     const int32_t* __restrict__ tix = reinterpret_cast<const int32_t*>(a.scratch + (int64_t)a.n_nets * rows * Jn * CH);
@@ -253,11 +229,7 @@ extern "C" int iplan_enc_saliency(const IplanEncSaliencyArgs* a, iplan_stream_t 
                     a->n_nets, a->E, a->N, a->T, a->L, a->d, a->Z, a->K, a->nW, IPLAN_ENC_SAL_MAX_L);
     if (!a->hist || !a->enc_params || !a->windows || !a->windows_host || !a->scratch)
         return fail(IPLAN_EINVAL, "iplan_enc_saliency: null tensor pointer (hist, enc_params, windows, windows_host or scratch)");
-    for (int w = 0; w < a->nW; ++w) {
-        const int32_t j = a->windows_host[w];
-        if (j < 0 || j >= J) return fail(IPLAN_EINVAL, "iplan_enc_saliency: windows[%d]=%d outside [0, J=%lld)", w, j, (long long)J);
-        if (w > 0 && j <= a->windows_host[w - 1]) return fail(IPLAN_EINVAL, "iplan_enc_saliency: windows must be sorted and distinct (entry %d)", w);
-    }
+    if (const int rc = enc_chain_check_list("iplan_enc_saliency", "windows", a->windows_host, a->nW, J)) return rc;
     if (!a->seed && (a->seed_index < -1 || a->seed_index >= a->Z))
         return fail(IPLAN_EINVAL, "iplan_enc_saliency: seed_index=%d outside [-1, Z=%d)", a->seed_index, a->Z);
     if (a->seed && a->target_index) return fail(IPLAN_EINVAL, "iplan_enc_saliency: target_index is only defined without a seed tensor");

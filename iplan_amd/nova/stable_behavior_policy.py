@@ -17,6 +17,85 @@ from .prediction_policy import _as_dev
 EPS = 1e-10
 
 
+def _history_dims(who, entry, policy, history):
+    """``history`` [E, T, nA, N, d] (numpy or tensor) fits ``policy`` and ``entry``'s window limit -> (as_np, E, T, nA, N, d, J)"""
+    as_np = isinstance(history, np.ndarray)
+    if not as_np and not torch.is_tensor(history):
+        raise ValueError(f"{who}: history must be a numpy array or a tensor [E, T, nA, N, d]")
+    if history.ndim != 5:
+        raise ValueError(f"{who}: history must be [E, T, nA, N, d], got {tuple(history.shape)}")
+    E, T, nA, N, d = (int(s) for s in history.shape)
+    Lw = policy.max_history_len
+    J = T - 1 - Lw
+    if nA != policy.n_agents or d != policy.args.obs_shape_single or E < 1 or N < 1:
+        raise ValueError(f"{who}: history {tuple(history.shape)} does not fit n_agents={policy.n_agents}, d={policy.args.obs_shape_single}")
+    if J < 1:
+        raise ValueError(f"{who}: T={T} leaves no window (J = T - 1 - L = {J})")
+    if Lw > ops.L.ENC_SAL_MAX_L:
+        raise NotImplementedError(f"{who}: max_history_len={Lw} > {ops.L.ENC_SAL_MAX_L} is not supported by {entry}")
+    return as_np, E, T, nA, N, d, J
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _as_int(who, v, what):
+    if not _is_int(v):
+        raise ValueError(f"{who}: {what} must be an int, got {v!r}")
+    return int(v)
+
+
+def _int_list(who, v, what, entry, kinds="an int or a sequence of ints", text=False):
+    """an int or a sequence of ints -> list; ``entry`` names an element and ``kinds`` what is accepted in the messages; ``text``: a str is
+    taken as a sequence (and refused character by character), not refused as a whole"""
+    if _is_int(v):
+        return [int(v)]
+    if not text and isinstance(v, (str, bytes)):
+        raise ValueError(f"{who}: {what} must be {kinds}, got {v!r}")
+    try:
+        return [_as_int(who, j, entry) for j in list(v)]
+    except TypeError:
+        raise ValueError(f"{who}: {what} must be {kinds}, got {v!r}") from None
+
+
+def _sorted_inside(who, idx, what, J):
+    if not idx or any(j < 0 or j >= J for j in idx) or any(b <= a for a, b in zip(idx, idx[1:])):
+        raise ValueError(f"{who}: {what} must be sorted, distinct and inside [0, J={J}), got {idx}")
+
+
+def _net_major(h, d):
+    """[E, T, nA, N, d] -> the [nA, E, T, N, d] view the encoder ops read in place (a copy where the (N, d) rows are not contiguous)"""
+    hist = h.permute(2, 0, 1, 3, 4)
+    return hist if hist.stride(4) == 1 and hist.stride(3) == d else hist.contiguous()
+
+
+def _chunks(who, E, n, shared, each, max_workspace_mb, item):
+    """Envs first; where ONE env with all ``n`` items does not fit under ``max_workspace_mb``, groups of items as well.  ``shared``:
+    floats per env whatever the number of items, ``each``: floats per env and item -> (envs per chunk, [(first, end) of every group])"""
+    limit = int(max_workspace_mb * 2 ** 20) // 4
+    per_env = shared + n * each
+    if per_env <= limit:
+        return min(E, limit // per_env), [(0, n)]
+    g = (limit - shared) // each
+    if g < 1:
+        raise ValueError(f"{who}: max_workspace_mb={max_workspace_mb} is too small for one env and one {item} ({4 * (shared + each)} bytes)")
+    return 1, [(i, min(n, i + g)) for i in range(0, n, g)]
+
+
+def _to_numpy(res):
+    """a dict of device tensors as host arrays of the matching dtypes, by ONE read-back (every piece is exactly representable in float64)"""
+    keys = list(res)
+    host = torch.cat([res[k].reshape(-1).double() for k in keys]).cpu().numpy()
+    out_np, at = {}, 0
+    for k in keys:
+        n = res[k].numel()
+        piece = host[at:at + n].reshape(tuple(res[k].shape))
+        at += n
+        out_np[k] = piece.astype({torch.float32: np.float32, torch.int64: np.int64, torch.bool: np.bool_}.get(res[k].dtype, np.float64))
+    return out_np
+
+
 class Behavior_policy:
     def __init__(self, args, logger):
         self.device = torch.device("cuda" if args.use_cuda else "cpu")
@@ -416,51 +495,26 @@ class Behavior_policy:
         ``max_workspace_mb``; chunked and unchunked calls give the same bits.  Deterministic; draws from no generator; no parameter,
         gradient, optimiser or carried state is touched; a data-parallel ``dp`` attachment is not consulted."""
         self.join_decoder()
-        as_np = isinstance(history, np.ndarray)
-        if not as_np and not torch.is_tensor(history):
-            raise ValueError("latent_saliency: history must be a numpy array or a tensor [E, T, nA, N, d]")
-        if history.ndim != 5:
-            raise ValueError(f"latent_saliency: history must be [E, T, nA, N, d], got {tuple(history.shape)}")
-        E, T, nA, N, d = (int(s) for s in history.shape)
+        who = "latent_saliency"
+        as_np, E, T, nA, N, d, J = _history_dims(who, "iplan_enc_saliency", self, history)
         Lw, Z, dev = self.max_history_len, self.latent_dim, self.device
-        J = T - 1 - Lw
-        if nA != self.n_agents or d != self.args.obs_shape_single or E < 1 or N < 1:
-            raise ValueError(f"latent_saliency: history {tuple(history.shape)} does not fit n_agents={self.n_agents}, d={self.args.obs_shape_single}")
-        if J < 1:
-            raise ValueError(f"latent_saliency: T={T} leaves no window (J = T - 1 - L = {J})")
-        if Lw > ops.L.ENC_SAL_MAX_L:
-            raise NotImplementedError(f"latent_saliency: max_history_len={Lw} > {ops.L.ENC_SAL_MAX_L} is not supported by iplan_enc_saliency")
-
-        def as_int(v, what):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"latent_saliency: {what} must be an int, got {v!r}")
-            return int(v)
-        if windows is None:
-            win = [J - 1]
-        elif isinstance(windows, (int, np.integer)) and not isinstance(windows, (bool, np.bool_)):
-            win = [int(windows)]
-        else:
-            try:
-                win = [as_int(j, "a window") for j in list(windows)]
-            except TypeError:
-                raise ValueError(f"latent_saliency: windows must be None, an int or a sequence of ints, got {windows!r}") from None
-        if not win or any(j < 0 or j >= J for j in win) or any(b <= a for a, b in zip(win, win[1:])):
-            raise ValueError(f"latent_saliency: windows must be sorted, distinct and inside [0, J={J}), got {win}")
+        win = [J - 1] if windows is None else _int_list(who, windows, "windows", "a window", kinds="None, an int or a sequence of ints", text=True)
+        _sorted_inside(who, win, "windows", J)
         W = len(win)
-        K = max(win) if lags is None else as_int(lags, "lags")
+        K = max(win) if lags is None else _as_int(who, lags, "lags")
         if K < 0:
             raise ValueError(f"latent_saliency: lags={K} is negative")
         R = K + Lw
         want = (want,) if isinstance(want, str) else tuple(want)
         if any(k not in ("step", "grad", "act") for k in want):
             raise ValueError(f"latent_saliency: want={want} -- known: 'step', 'grad', 'act'")
-        if presence_col is not None and not 0 <= as_int(presence_col, "presence_col") < d:
+        if presence_col is not None and not 0 <= _as_int(who, presence_col, "presence_col") < d:
             raise ValueError(f"latent_saliency: presence_col={presence_col} outside [0, d={d})")
         seed_index, seed_full = -1, None
         if isinstance(target, str):
             if target != "argmax":
                 raise ValueError(f"latent_saliency: target={target!r} -- 'argmax', an int or a tensor [E, W, nA, N, Z]")
-        elif isinstance(target, (int, np.integer)) and not isinstance(target, (bool, np.bool_)):
+        elif _is_int(target):
             seed_index = int(target)
             if not 0 <= seed_index < Z:
                 raise ValueError(f"latent_saliency: target={seed_index} outside [0, Z={Z})")
@@ -473,10 +527,7 @@ class Behavior_policy:
         if not (isinstance(max_workspace_mb, (int, float)) and max_workspace_mb > 0):
             raise ValueError(f"latent_saliency: max_workspace_mb={max_workspace_mb!r} must be positive")
 
-        h = _as_dev(history, dev)
-        hist = h.permute(2, 0, 1, 3, 4)                                            # [nA, E, T, N, d] view
-        if hist.stride(4) != 1 or hist.stride(3) != d:
-            hist = hist.contiguous()
+        hist = _net_major(_as_dev(history, dev), d)
         names = ["step_l1", "carry_l2", "latent"]
         names += ["step_gxi", "feature_l1"] if "step" in want else []
         names += ["grad"] if "grad" in want else []
@@ -485,18 +536,9 @@ class Behavior_policy:
         tail = dict(grad=(R, d), step_l1=(R,), step_gxi=(R,), feature_l1=(d,), carry_l2=(), latent=(Z,), target_index=(), active=(K + 1, Lw))
         # chunks: envs first; where ONE env with all windows does not fit, groups of windows as well.  Counted against the limit: the
         # kernel's scratch (he_j of windows 0 .. max(windows), one index per slot) and the chunk's own output buffers.
-        limit = int(max_workspace_mb * 2 ** 20) // 4
         out_w = nA * N * sum(int(np.prod(tail[k])) for k in names)                  # output floats per env and window
         he_env = ops.enc_saliency_scratch_floats(nA, N, win[-1:]) - nA * N           # scratch floats per env that all windows share
-        per_env = he_env + W * (nA * N + out_w)
-        if per_env <= limit:
-            Ec, groups = min(E, limit // per_env), [(0, W)]
-        else:
-            Ec, g = 1, (limit - he_env) // (nA * N + out_w)
-            if g < 1:
-                raise ValueError(f"latent_saliency: max_workspace_mb={max_workspace_mb} is too small for one env and one window "
-                                 f"({4 * (he_env + nA * N + out_w)} bytes)")
-            groups = [(w, min(W, w + g)) for w in range(0, W, g)]
+        Ec, groups = _chunks(who, E, W, he_env, nA * N + out_w, max_workspace_mb, "window")
         full = {k: torch.empty((nA, E, N, W) + tail[k], dtype=torch.int32 if k in ("target_index", "active") else torch.float32, device=dev)
                 for k in names}
         for e0 in range(0, E, Ec):
@@ -527,18 +569,7 @@ class Behavior_policy:
         if "target_index" in res:
             res["target_index"] = res["target_index"].to(torch.int64)
         res["step_valid"], res["lag_l1"] = step_valid, lag_l1
-        if not as_np:
-            return res
-        # numpy callers: ONE read-back (every piece is exactly representable in float64)
-        keys = list(res)
-        host = torch.cat([res[k].reshape(-1).double() for k in keys]).cpu().numpy()
-        out_np, at = {}, 0
-        for k in keys:
-            n = res[k].numel()
-            piece = host[at:at + n].reshape(tuple(res[k].shape))
-            at += n
-            out_np[k] = piece.astype({torch.float32: np.float32, torch.int64: np.int64, torch.bool: np.bool_}.get(res[k].dtype, np.float64))
-        return out_np
+        return _to_numpy(res) if as_np else res
 
     def latent_knockout(self, history, starts, duration=1, horizon=None, columns=None, baseline=None, want=("shift",), presence_col=0,
                         max_workspace_mb=256):
@@ -571,43 +602,16 @@ class Behavior_policy:
         ``max_workspace_mb``; chunked and unchunked calls give the same bits.  Deterministic; draws from no generator; no parameter,
         gradient, optimiser or carried state is touched; a data-parallel ``dp`` attachment is not consulted."""
         self.join_decoder()
-        as_np = isinstance(history, np.ndarray)
-        if not as_np and not torch.is_tensor(history):
-            raise ValueError("latent_knockout: history must be a numpy array or a tensor [E, T, nA, N, d]")
-        if history.ndim != 5:
-            raise ValueError(f"latent_knockout: history must be [E, T, nA, N, d], got {tuple(history.shape)}")
-        E, T, nA, N, d = (int(s) for s in history.shape)
+        who = "latent_knockout"
+        as_np, E, T, nA, N, d, J = _history_dims(who, "iplan_enc_knockout", self, history)
         Lw, Z, dev = self.max_history_len, self.latent_dim, self.device
-        J = T - 1 - Lw
-        if nA != self.n_agents or d != self.args.obs_shape_single or E < 1 or N < 1:
-            raise ValueError(f"latent_knockout: history {tuple(history.shape)} does not fit n_agents={self.n_agents}, d={self.args.obs_shape_single}")
-        if J < 1:
-            raise ValueError(f"latent_knockout: T={T} leaves no window (J = T - 1 - L = {J})")
-        if Lw > ops.L.ENC_SAL_MAX_L:
-            raise NotImplementedError(f"latent_knockout: max_history_len={Lw} > {ops.L.ENC_SAL_MAX_L} is not supported by iplan_enc_knockout")
-
-        def as_int(v, what):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"latent_knockout: {what} must be an int, got {v!r}")
-            return int(v)
-
-        def int_list(v, what):
-            if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)):
-                return [int(v)]
-            if isinstance(v, (str, bytes)):
-                raise ValueError(f"latent_knockout: {what} must be an int or a sequence of ints, got {v!r}")
-            try:
-                return [as_int(j, f"an entry of {what}") for j in list(v)]
-            except TypeError:
-                raise ValueError(f"latent_knockout: {what} must be an int or a sequence of ints, got {v!r}") from None
-        st = int_list(starts, "starts")
-        if not st or any(s < 0 or s >= J for s in st) or any(b <= a for a, b in zip(st, st[1:])):
-            raise ValueError(f"latent_knockout: starts must be sorted, distinct and inside [0, J={J}), got {st}")
+        st = _int_list(who, starts, "starts", "an entry of starts")
+        _sorted_inside(who, st, "starts", J)
         Q = len(st)
-        D = as_int(duration, "duration")
+        D = _as_int(who, duration, "duration")
         if D < 1:
             raise ValueError(f"latent_knockout: duration={D} must be at least 1")
-        H = J - st[0] if horizon is None else as_int(horizon, "horizon")
+        H = J - st[0] if horizon is None else _as_int(who, horizon, "horizon")
         if H < 1:
             raise ValueError(f"latent_knockout: horizon={H} must be at least 1")
         if columns is None:
@@ -615,13 +619,13 @@ class Behavior_policy:
         else:
             if isinstance(columns, (int, np.integer)):
                 raise ValueError(f"latent_knockout: columns must be None or a sequence of ints, got {columns!r}")
-            cols = int_list(columns, "columns")
+            cols = _int_list(who, columns, "columns", "an entry of columns")
             if not cols or any(c < 0 or c >= d for c in cols) or len(set(cols)) != len(cols):
                 raise ValueError(f"latent_knockout: columns must be distinct and inside [0, d={d}), got {cols}")
         want = (want,) if isinstance(want, str) else tuple(want)
         if any(k not in ("shift", "latent_ko", "hidden_ko") for k in want):
             raise ValueError(f"latent_knockout: want={want} -- known: 'shift', 'latent_ko', 'hidden_ko'")
-        if presence_col is not None and not 0 <= as_int(presence_col, "presence_col") < d:
+        if presence_col is not None and not 0 <= _as_int(who, presence_col, "presence_col") < d:
             raise ValueError(f"latent_knockout: presence_col={presence_col} outside [0, d={d})")
         hold, base_row = False, None
         if isinstance(baseline, str):
@@ -639,10 +643,7 @@ class Behavior_policy:
         if isinstance(max_workspace_mb, (bool, np.bool_)) or not (isinstance(max_workspace_mb, (int, float)) and max_workspace_mb > 0):
             raise ValueError(f"latent_knockout: max_workspace_mb={max_workspace_mb!r} must be positive")
 
-        h = _as_dev(history, dev)
-        hist = h.permute(2, 0, 1, 3, 4)                                            # [nA, E, T, N, d] view, read in place
-        if hist.stride(4) != 1 or hist.stride(3) != d:
-            hist = hist.contiguous()
+        hist = _net_major(_as_dev(history, dev), d)
         Jn = ops.enc_knockout_windows(J, st, H)
         names = ["latent", "intent_base", "intent", "latent_shift_sq", "state_shift_sq"]
         names += [k for k in ("latent_ko", "hidden_ko") if k in want]
@@ -650,18 +651,9 @@ class Behavior_policy:
         # chunks: envs first; where ONE env with all jobs does not fit, groups of jobs as well (each group walks the base chain as far
         # as it needs).  Counted against the limit: the kernel's workspace (he_j of windows 0 .. Jn-1), the base chain's outputs and
         # the chunk's per-job outputs.
-        limit = int(max_workspace_mb * 2 ** 20) // 4
         slot = nA * N * H * sum(int(np.prod(tail[k])) for k in names[2:])           # output floats per env and job
         base_env = nA * N * Jn * (32 + Z + 1)                                       # workspace and base outputs per env
-        per_env = base_env + Q * slot
-        if per_env <= limit:
-            Ec, groups = min(E, limit // per_env), [(0, Q)]
-        else:
-            Ec, g = 1, (limit - base_env) // slot
-            if g < 1:
-                raise ValueError(f"latent_knockout: max_workspace_mb={max_workspace_mb} is too small for one env and one job "
-                                 f"({4 * (base_env + slot)} bytes)")
-            groups = [(q, min(Q, q + g)) for q in range(0, Q, g)]
+        Ec, groups = _chunks(who, E, Q, base_env, slot, max_workspace_mb, "job")
         f32, i32 = torch.float32, torch.int32
         full = {k: torch.zeros((nA, E, N, Q, H) + tail[k], dtype=i32 if k == "intent" else f32, device=dev) for k in names[2:]}
         full["latent"] = torch.empty(nA, E, N, Jn, Z, dtype=f32, device=dev)
@@ -715,20 +707,10 @@ class Behavior_policy:
             mean = torch.where(ctot > 0, tot / ctot.clamp(min=1.0), torch.zeros_like(tot))
             res["echo_shift"], res["echo_flip_rate"] = mean[0], mean[1]
         meta = {"window": (D, H), "direct_windows": min(H, D + Lw - 1)}
-        if not as_np:
-            res.update(meta)
-            return res
-        # numpy callers: ONE read-back (every piece is exactly representable in float64)
-        keys = list(res)
-        host = torch.cat([res[k].reshape(-1).double() for k in keys]).cpu().numpy()
-        out_np, at = {}, 0
-        for k in keys:
-            n = res[k].numel()
-            piece = host[at:at + n].reshape(tuple(res[k].shape))
-            at += n
-            out_np[k] = piece.astype({torch.float32: np.float32, torch.int64: np.int64, torch.bool: np.bool_}.get(res[k].dtype, np.float64))
-        out_np.update(meta)
-        return out_np
+        if as_np:
+            res = _to_numpy(res)
+        res.update(meta)
+        return res
 
     # ---------------------------------------------------------------------------- checkpoints
     def save_models(self, path):

@@ -775,6 +775,31 @@ def _job_list(a, jobs, N, dev):
     return j_host, j_dev
 
 
+def _enc_rows(a, enc_arena, hist, L_win, Z, coef):
+    """What every launch over the behaviour encoder's chain checks and enters into its descriptor ``a``: hist [n_nets, E, T, N, d] with
+    contiguous (N, d) rows, the sizes, the history's strides, ``coef``, the encoder's arena and its offsets -> hist's shape"""
+    n_nets, E, T, N, d = hist.shape
+    assert hist.dtype == torch.float32 and hist.stride(4) == 1 and hist.stride(3) == d
+    a.n_nets, a.E, a.N, a.T, a.L, a.d, a.Z = n_nets, E, N, T, L_win, d, Z
+    a.hist, a.h_s_net, a.h_s_e, a.h_s_t = hist.data_ptr(), hist.stride(0), hist.stride(1), hist.stride(2)
+    a.coef = coef
+    a.enc_params, a.enc_s_net = enc_arena.data.data_ptr(), enc_arena.net_stride
+    for i, k in enumerate(L.ENC_PARAM_ORDER):
+        a.enc_off[i] = enc_arena.off(k)
+    return n_nets, E, T, N, d
+
+
+def _index_list(a, name, idx, dev):
+    """``idx`` as ints, entered into the descriptor ``a`` as ``name`` (the device copy the kernel reads; null for an empty list) and
+    ``name``_host (the host copy the entry point checks) -> (the ints, both copies, to be kept alive)"""
+    idx = [int(i) for i in idx]
+    i_host = (C.c_int32 * max(len(idx), 1))(*idx)
+    i_dev = torch.tensor(idx, dtype=torch.int32, device=dev) if idx else None
+    setattr(a, name, L.ptr(i_dev))
+    setattr(a, name + "_host", C.cast(i_host, C.c_void_p))
+    return idx, i_host, i_dev
+
+
 def _per_source(seq, n_src, what):
     """``seq`` (None: nothing) as one entry per source of the rows; it may be shorter, and longer only with nothing past the end"""
     seq = (None,) * n_src if seq is None else tuple(seq)
@@ -2109,20 +2134,14 @@ def beh_eval(enc_arena, dec_arena, hist, mask, L_win, Z, coef, thres, want_laten
     output, sums [n_nets, J, L, 2] = per (window, look-ahead step) the masked L1 error sum and the clamped distance sum), None
     for what was not asked for."""
     lib = _lib(lib)
-    n_nets, E, T, N, d = hist.shape
     assert want_latent or want_recon or want_sums, "beh_eval: no output asked for"
-    assert hist.dtype == torch.float32 and hist.stride(4) == 1 and hist.stride(3) == d
+    a = L.BehEvalArgs()
+    n_nets, E, T, N, d = _enc_rows(a, enc_arena, hist, L_win, Z, coef)
     dev = hist.device
     f32 = dict(dtype=torch.float32, device=dev)
     J = T - 1 - L_win
     rows = E * N
-    a = L.BehEvalArgs()
-    a.n_nets, a.E, a.N, a.T, a.L, a.d, a.Z = n_nets, E, N, T, L_win, d, Z
-    a.hist, a.h_s_net, a.h_s_e, a.h_s_t = hist.data_ptr(), hist.stride(0), hist.stride(1), hist.stride(2)
-    a.coef, a.thres = coef, thres
-    a.enc_params, a.enc_s_net = enc_arena.data.data_ptr(), enc_arena.net_stride
-    for i, k in enumerate(L.ENC_PARAM_ORDER):
-        a.enc_off[i] = enc_arena.off(k)
+    a.thres = thres
     a.dec_params, a.dec_s_net = dec_arena.data.data_ptr(), dec_arena.net_stride
     for i, k in enumerate(L.DEC_PARAM_ORDER):
         a.dec_off[i] = dec_arena.off(k)
@@ -2165,43 +2184,28 @@ def enc_saliency(enc_arena, hist, windows, K, L_win, Z, coef, seed=None, seed_in
     active int32 [n_nets, E*N, nW, K+1, L_win] (a 32-bit mask), None for what was not asked for.  ``out``: optional dict of
     destination tensors of exactly those shapes (contiguous) for some of the wanted names."""
     lib = _lib(lib)
-    n_nets, E, T, N, d = hist.shape
-    assert hist.dtype == torch.float32 and hist.stride(4) == 1 and hist.stride(3) == d
+    a = L.EncSaliencyArgs()
+    n_nets, E, T, N, d = _enc_rows(a, enc_arena, hist, L_win, Z, coef)
     assert all(k in ENC_SAL_OUTPUTS for k in want), want
     dev = hist.device
-    windows = [int(j) for j in windows]
+    windows, w_host, w_dev = _index_list(a, "windows", windows, dev)
     nW, rows, R = len(windows), E * N, K + L_win
-    a = L.EncSaliencyArgs()
-    a.n_nets, a.E, a.N, a.T, a.L, a.d, a.Z, a.K, a.nW = n_nets, E, N, T, L_win, d, Z, K, nW
-    a.hist, a.h_s_net, a.h_s_e, a.h_s_t = hist.data_ptr(), hist.stride(0), hist.stride(1), hist.stride(2)
+    a.K, a.nW = K, nW
     # the kernel reads steps 0 .. max(windows) of every (net, env): they must lie inside the history's storage
     if nW and 0 <= max(windows) < T and min(hist.stride(0), hist.stride(1), hist.stride(2)) >= 0:
         _inside(hist, (n_nets - 1) * hist.stride(0) + (E - 1) * hist.stride(1) + max(windows) * hist.stride(2) + N * d, "enc_saliency: hist")
-    w_host = (C.c_int32 * max(nW, 1))(*windows)
-    w_dev = torch.tensor(windows, dtype=torch.int32, device=dev) if nW else None
-    a.windows, a.windows_host = L.ptr(w_dev), C.cast(w_host, C.c_void_p)
     if seed is not None:
         assert seed.dtype == torch.float32 and seed.device == dev and seed.is_contiguous() and seed.shape == (n_nets, rows, nW, Z), seed.shape
         a.seed = seed.data_ptr()
-    a.seed_index, a.coef = int(seed_index), coef
-    a.enc_params, a.enc_s_net = enc_arena.data.data_ptr(), enc_arena.net_stride
-    for i, k in enumerate(L.ENC_PARAM_ORDER):
-        a.enc_off[i] = enc_arena.off(k)
+    a.seed_index = int(seed_index)
     floats = enc_saliency_scratch_floats(n_nets, rows, windows) if nW and 0 <= max(windows) < T else 0
     scratch = torch.empty(max(floats, 4), dtype=torch.float32, device=dev)      # (an inspection call: not kept between calls)
     a.scratch, a.scratch_floats = scratch.data_ptr(), floats
     shapes = dict(grad=(R, d), step_l1=(R,), step_gxi=(R,), feature_l1=(d,), carry_l2=(), latent=(Z,), target_index=(), active=(K + 1, L_win))
     res = {k: None for k in ENC_SAL_OUTPUTS}
     for k in want:
-        shape = (n_nets, rows, nW) + shapes[k]
         dt = torch.float32 if k not in ("target_index", "active") else torch.int32
-        if out is not None and k in out:
-            t = out[k]
-            assert t.shape == shape and t.dtype == dt and t.is_contiguous() and t.device == dev, (k, t.shape, shape)
-        else:
-            t = torch.empty(shape, dtype=dt, device=dev)
-        res[k] = t
-        setattr(a, k, t.data_ptr())
+        setattr(a, k, _dest(out, res, k, (n_nets, rows, nW) + shapes[k], dt, dev))
     _launch("enc_saliency_kernel", lambda: lib.call("iplan_enc_saliency", a, L.current_stream(dev)))
     res["_args"] = a
     res["_keep"] = (hist, w_host, w_dev, seed, scratch)
@@ -2234,24 +2238,19 @@ def enc_knockout(enc_arena, hist, starts, D, H, L_win, Z, coef, columns=None, ba
     (contiguous) -- the kernel writes only the slots that exist, so the caller prepares the others; ``workspace``: an optional
     float32 tensor of at least enc_knockout_workspace_floats(...) elements."""
     lib = _lib(lib)
-    n_nets, E, T, N, d = hist.shape
-    assert hist.dtype == torch.float32 and hist.stride(4) == 1 and hist.stride(3) == d
+    a = L.EncKnockoutArgs()
+    n_nets, E, T, N, d = _enc_rows(a, enc_arena, hist, L_win, Z, coef)
     want = tuple(dict.fromkeys(("latent",) + tuple(want)))
     assert all(k in ENC_KO_OUTPUTS for k in want), want
     dev = hist.device
-    starts = [int(s) for s in starts]
+    starts, s_host, s_dev = _index_list(a, "starts", starts, dev)
     Q, rows, J = len(starts), E * N, T - 1 - L_win
     ok = Q > 0 and J >= 1 and H >= 1 and all(0 <= s < J for s in starts)          # (everything else is refused by the entry point)
     Jn = enc_knockout_windows(J, starts, H) if ok else 0
-    a = L.EncKnockoutArgs()
-    a.n_nets, a.E, a.N, a.T, a.L, a.d, a.Z, a.Q, a.D, a.H = n_nets, E, N, T, L_win, d, Z, Q, D, H
-    a.hist, a.h_s_net, a.h_s_e, a.h_s_t = hist.data_ptr(), hist.stride(0), hist.stride(1), hist.stride(2)
+    a.Q, a.D, a.H = Q, D, H
     # the kernel reads steps 0 .. Jn-1 of every (net, env): they must lie inside the history's storage
     if ok and min(hist.stride(0), hist.stride(1), hist.stride(2)) >= 0:
         _inside(hist, (n_nets - 1) * hist.stride(0) + (E - 1) * hist.stride(1) + (Jn - 1) * hist.stride(2) + N * d, "enc_knockout: hist")
-    s_host = (C.c_int32 * max(Q, 1))(*starts)
-    s_dev = torch.tensor(starts, dtype=torch.int32, device=dev) if Q else None
-    a.starts, a.starts_host = L.ptr(s_dev), C.cast(s_host, C.c_void_p)
     cols = list(range(d)) if columns is None else [int(c) for c in columns]
     assert all(0 <= c < 32 for c in cols), cols
     a.col_mask = sum(1 << c for c in set(cols))
@@ -2259,10 +2258,6 @@ def enc_knockout(enc_arena, hist, starts, D, H, L_win, Z, coef, columns=None, ba
     if baseline is not None:
         assert baseline.dtype == torch.float32 and baseline.device == dev and baseline.is_contiguous() and baseline.shape == (n_nets, d), baseline.shape
         a.baseline = baseline.data_ptr()
-    a.coef = coef
-    a.enc_params, a.enc_s_net = enc_arena.data.data_ptr(), enc_arena.net_stride
-    for i, k in enumerate(L.ENC_PARAM_ORDER):
-        a.enc_off[i] = enc_arena.off(k)
     floats = n_nets * rows * Jn * 32
     if workspace is None:
         workspace = torch.empty(max(floats, 4), dtype=torch.float32, device=dev)   # (an inspection call: not kept between calls)
@@ -2274,17 +2269,9 @@ def enc_knockout(enc_arena, hist, starts, D, H, L_win, Z, coef, columns=None, ba
                   state_shift_sq=(Q, Hs))
     res = {k: None for k in ENC_KO_OUTPUTS}
     for k in want:
-        shape = (n_nets, rows) + shapes[k]
         dt = torch.int32 if k in ("intent_base", "intent") else torch.float32
-        if out is not None and k in out:
-            t = out[k]
-            assert t.shape == shape and t.dtype == dt and t.is_contiguous() and t.device == dev, (k, t.shape, shape)
-        elif k in ("latent", "intent_base"):
-            t = torch.empty(shape, dtype=dt, device=dev)
-        else:
-            t = torch.zeros(shape, dtype=dt, device=dev)                            # slots of windows past J stay zero
-        res[k] = t
-        setattr(a, k, t.data_ptr())
+        fresh = torch.empty if k in ("latent", "intent_base") else torch.zeros      # slots of windows past J stay zero
+        setattr(a, k, _dest(out, res, k, (n_nets, rows) + shapes[k], dt, dev, fresh=fresh))
     _launch("enc_knockout_kernel", lambda: lib.call("iplan_enc_knockout", a, L.current_stream(dev)))
     res["_args"] = a
     res["_keep"] = (hist, s_host, s_dev, baseline, workspace)
