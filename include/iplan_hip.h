@@ -1490,6 +1490,55 @@ typedef struct {
 int iplan_gat_knockout_trace(const IplanGatKnockoutTraceArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Forecasts of the knocked chains through time (csrc/predict_knockout.hip): iplan_predict's decoder chain
+ *   y_p, h = Linear(tanh(GRU(ReLU(Linear(y_{p-1})), h))),  p < P,
+ * run on the latents iplan_gat_knockout_trace wrote, reduced where it runs to P numbers per row.  A row is (net, b, job slot q, window
+ * step h, entity i) -- the order of a contiguous latent_ko [n_nets, B, J, H, N, 32]; one wave walks 16 rows of one net.  Per row
+ *   h_0    = latent_ko row (net, b, q, h, i)
+ *   y_{-1} = history row (net, b, start + h, i): history + net*hist_s_net + b*hist_s_b + (start + h)*hist_s_step + i*hist_s_ent, d
+ *            contiguous floats of any alignment, read in place.  It is NEVER knocked, whatever the job was: the result isolates the
+ *            social path (Prediction_policy.attention_knockout's rule).
+ * The job list itself is not an argument: the knock is in latent_ko already.
+ * Outputs, each optional (NULL = not wanted; at least one is), element (net, b, q, h) at ptr + net*s_net + b*s_b + q*s_job + h*s_step:
+ *   fshift_sq [N, P]    sum over k < n_pos of (y_p[pos[k]] - pred_base_p[pos[k]])^2, k ascending, every difference, product and sum
+ *                       rounded on its own (no fma), so that the plain fp32 host loop gives the same bits.  Needs pred_base: rows
+ *                       (net, b, h) [N, P, d] at pred_base + net*pb_s_net + b*pb_s_b + h*pb_s_step, the forecasts of the walk with
+ *                       nothing knocked, written by an EARLIER launch (iplan_predict's pred on iplan_gat_trace's latent).
+ *   ferr_sq   [N, P]    the same sum against the recorded future, history row (net, b, start + h + 1 + p, i).  Where that step is not
+ *                       recorded (start + h + 1 + p >= S) the entry is +0.0 and nothing is read for it.  Needs S, the number of
+ *                       recorded steps of `history`, with start + H <= S.
+ *   pred_ko   [N, P, d] the forecasts themselves, bit for bit iplan_predict's on the same h_0 and start state.
+ * No atomics, no sums across rows: a slot's bits depend on its row and the arguments only.
+ * Refused: null args or tensors, no output, fshift_sq without pred_base, ferr_sq without a readable window (S < start + H), d outside
+ * [1, 16], n_nets outside [1, IPLAN_MAX_NETS], B / J / H / N / P < 1, start < 0, B*J*H*N > 2^31 - 17, n_pos outside [1, 16] (with
+ * fshift_sq or ferr_sq), a pos entry outside [0, d) or repeated, latent_ko misaligned (16 bytes, strides % 4 == 0).
+ */
+typedef struct {
+    int32_t n_nets, B, J, H, N, P, d;
+    int32_t S;                  /* recorded steps of `history`; only read with ferr_sq                     */
+    int32_t start;              /* first step of the window                                                */
+    int32_t n_pos;
+    int32_t pos[16];            /* the columns of the distance, in the order they are added                */
+    const float* history;
+    int64_t hist_s_net, hist_s_b, hist_s_step, hist_s_ent;
+    const float* latent_ko;     /* [N, 32] per (net, b, q, h)                                              */
+    int64_t lat_s_net, lat_s_b, lat_s_job, lat_s_step;
+    const float* pred_base;     /* [N, P, d] per (net, b, h), or NULL                                      */
+    int64_t pb_s_net, pb_s_b, pb_s_step;
+    const float* params;        /* decoder arena, IPLAN_DEC_* offsets                                      */
+    int64_t params_s_net;
+    int64_t off[IPLAN_DEC_NPARAM];
+    float* fshift_sq;
+    int64_t fs_s_net, fs_s_b, fs_s_job, fs_s_step;
+    float* ferr_sq;
+    int64_t fe_s_net, fe_s_b, fe_s_job, fe_s_step;
+    float* pred_ko;
+    int64_t pk_s_net, pk_s_b, pk_s_job, pk_s_step;
+} IplanPredictKnockoutArgs;
+
+int iplan_predict_knockout(const IplanPredictKnockoutArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Policy knock-out (occlusion attribution of the actors and critics): every row (e, s, agent) of a recorded batch is run once per
  * JOB, forward only -- LN(F) -> fc1 -> act -> LN -> fc2 -> act -> LN -> GRU cell (state given, held) -> LN -> head -> masked softmax | V
  * -- with one entity's columns of the selected per-entity sources replaced AS THE FEATURES ARE GATHERED (csrc/policy_knockout.hip,

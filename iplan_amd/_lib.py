@@ -55,7 +55,7 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
                 "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
                 "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout", "iplan_ac_knockout_trace",
-                "iplan_gat_knockout_trace", "iplan_ac_knockout_chain", "iplan_enc_knockout"]
+                "iplan_gat_knockout_trace", "iplan_ac_knockout_chain", "iplan_enc_knockout", "iplan_predict_knockout"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -503,6 +503,20 @@ class GatKnockoutTraceArgs(C.Structure):
     ]
 
 
+class PredictKnockoutArgs(C.Structure):
+    _fields_ = [
+        ("n_nets", i32), ("B", i32), ("J", i32), ("H", i32), ("N", i32), ("P", i32), ("d", i32), ("S", i32), ("start", i32),
+        ("n_pos", i32), ("pos", i32 * 16),
+        ("history", fp), ("hist_s_net", i64), ("hist_s_b", i64), ("hist_s_step", i64), ("hist_s_ent", i64),
+        ("latent_ko", fp), ("lat_s_net", i64), ("lat_s_b", i64), ("lat_s_job", i64), ("lat_s_step", i64),
+        ("pred_base", fp), ("pb_s_net", i64), ("pb_s_b", i64), ("pb_s_step", i64),
+        ("params", fp), ("params_s_net", i64), ("off", i64 * len(DEC_PARAM_ORDER)),
+        ("fshift_sq", fp), ("fs_s_net", i64), ("fs_s_b", i64), ("fs_s_job", i64), ("fs_s_step", i64),
+        ("ferr_sq", fp), ("fe_s_net", i64), ("fe_s_b", i64), ("fe_s_job", i64), ("fe_s_step", i64),
+        ("pred_ko", fp), ("pk_s_net", i64), ("pk_s_b", i64), ("pk_s_job", i64), ("pk_s_step", i64),
+    ]
+
+
 PDEC_SAL_MAX_P = 30      # IPLAN_PDEC_SAL_MAX_P
 
 
@@ -624,4 +638,4 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanPdecSaliencyArgs": PdecSaliencyArgs, "IplanGatKnockoutArgs": GatKnockoutArgs,
                   "IplanAcKnockoutArgs": AcKnockoutArgs, "IplanAcKnockoutTraceArgs": AcKnockoutTraceArgs,
                   "IplanGatKnockoutTraceArgs": GatKnockoutTraceArgs, "IplanAcKnockoutChainArgs": AcKnockoutChainArgs,
-                  "IplanEncKnockoutArgs": EncKnockoutArgs}
+                  "IplanEncKnockoutArgs": EncKnockoutArgs, "IplanPredictKnockoutArgs": PredictKnockoutArgs}

@@ -685,7 +685,7 @@ class Prediction_policy:
 
     def attention_knockout_trace(self, history, behavior_latent=None, hidden0=None, entities=None, start=0, duration=1, horizon=None,
                                  sources=("history", "behavior"), baseline=None, noise=None, deterministic=True, tau=None, want=("shift",),
-                                 presence_col=0, max_workspace_mb=256):
+                                 presence_col=0, max_workspace_mb=256, forecast=False, pos=(1, 2)):
         """How long does the social context remember a vehicle?  Vehicle j is out of sight for ``duration`` = D steps from step
         ``start`` and visible again afterwards; the GAT walks steps start .. start + H - 1 (``horizon`` = H, None: up to the last step
         of ``history``; ``duration`` None: knocked throughout, D = H) once per entity j of ``entities`` (default: all N; duplicates
@@ -712,11 +712,36 @@ class Prediction_policy:
                                             present at step start + h and entity j is present in at least one knocked step (column
                                             ``presence_col`` of the history row non-zero; < 0: everything counts); the environments are
                                             added in environment order; NaN where nothing counts
+        ``forecast=True`` answers the occlusion question for the forecasts: how far do every ego's forecasts of the scene move while
+        j is out of sight and afterwards, and how much worse do they get against what then happened?  Per chunk one ``iplan_predict``
+        launch decodes the base walk's latents, and ``iplan_predict_knockout`` decodes every knocked chain's latent at every step of
+        the window where the walk wrote it, reducing each forecast to P numbers per pair and step in the kernel; the decoder's start
+        state, ``history[:, start + h]``, is read in place and never knocked (``attention_knockout``'s rule: the result isolates the
+        social path), the targets are ``history[:, start + h + 1 + p]``.  ``want`` may then be empty of the names above and accepts
+        "forecast_error" and "pred_ko" (ValueError without ``forecast=True``).  ``pos``: the columns of the distance, distinct, added
+        in the order given.  It adds, P = ``pred_length``:
+          ``pred`` [E,H,nA,N,P,d]           nothing knocked: bit for bit ``ops.predict`` on the window's ``latent``
+          ``forecast_shift`` [E,H,nA,N,J,P] the Euclidean distance over the ``pos`` columns between entity i's forecast with and without
+                                            j: torch's sqrt of the kernel's sum of squares (every difference, product and sum rounded
+                                            on its own; at H = D = 1 bit for bit ``attention_knockout(forecast=True)``'s)
+          ``forecast_summary`` float64 numpy [nA,H,P,2]   the mean of forecast_shift over pairs i != j and over i == j under ``summary``'s
+                                            counting rule, from float64 sums formed on the device per (agent, env, step, p) and added
+                                            over the environments on the host in environment order; NaN where nothing counts.
+                                            All summaries of a call share ONE read-back
+          with "forecast_error": ``forecast_error`` [E,H,nA,N,P] and ``forecast_error_ko`` [E,H,nA,N,J,P], the same distance between the
+                                            forecast (base, knocked) and the recorded future, +0.0 where the target step is not
+                                            recorded; ``forecast_valid`` bool numpy [H,P]: the target step start + h + 1 + p exists;
+                                            ``forecast_error_summary`` float64 numpy [nA,H,P,2]: the mean base error and the mean knocked
+                                            error over the pairs i != j that count, whose target exists and whose entity i is present
+                                            in the target row
+          with "pred_ko": ``pred_ko`` [E,H,nA,J,N,P,d]   the knocked chains' forecasts
+        With ``forecast=False`` nothing changes: the same launches, bits and keys.
         Environments and jobs are chunked so that what a chunk holds in flight stays under ``max_workspace_mb``; the bits do not depend
         on the chunking.  numpy in -> numpy out, device tensors in -> device tensors out.  Parameters, gradients, optimiser state,
-        carried state and (with ``deterministic=True``) torch's generator are not touched.  Not covered: knocking the hidden state,
-        the forecast continuation, aggregation across data-parallel ranks.  ``latent_ko`` over steps continues into the policy as
-        ``DcntrlMAC.knockout_trace``'s per-job override; its ``social=`` does both halves in one call."""
+        carried state and (with ``deterministic=True``) torch's generator are not touched.  Not covered: knocking the hidden state
+        or the decoder's start state, a chain into ``evaluate``'s sampling, horizon subsets, aggregation across data-parallel ranks.
+        ``latent_ko`` over steps continues into the policy as ``DcntrlMAC.knockout_trace``'s per-job override; its ``social=`` does
+        both halves in one call."""
         who = "attention_knockout_trace"
         as_np = isinstance(history, np.ndarray)
         dev = self.device
@@ -724,13 +749,21 @@ class Prediction_policy:
         if hist.dim() != 5:
             raise ValueError(f"{who}: history must be [E,S,nA,N,d], got {tuple(hist.shape)}")
         E, S, nA, N, d = hist.shape
-        A = self.args.attention_dim
+        A, P = self.args.attention_dim, self.pred_length
         if nA != self.n_agents or d != self.obs_shape or not 2 <= N <= ops.L.GAT_MAX_ENTITIES:
             raise ValueError(f"{who}: history {tuple(hist.shape)} does not fit n_agents={self.n_agents}, obs width {self.obs_shape}, "
                              f"2 <= N <= {ops.L.GAT_MAX_ENTITIES}")
+        want = tuple(want)
+        keep_err, keep_pk = "forecast_error" in want, "pred_ko" in want
+        if (keep_err or keep_pk) and not forecast:
+            raise ValueError(f"{who}: want={want} -- 'forecast_error' and 'pred_ko' need forecast=True")
+        want = tuple(k for k in want if k not in ("forecast_error", "pred_ko"))
         sources, knock, want, tau, jobs, rows = self._knock_spec(who, N, d, sources, want, noise, deterministic, tau, presence_col, entities, baseline)
         J = len(jobs)
         ints = (int, np.integer)
+        pos = tuple(pos) if forecast else ()
+        if forecast and (not pos or any(isinstance(c, bool) or not isinstance(c, ints) or not 0 <= c < d for c in pos) or len(set(pos)) != len(pos)):
+            raise ValueError(f"{who}: pos={pos} -- distinct columns in [0, {d}), at least one")
         if not isinstance(start, ints) or not 0 <= start < S:
             raise ValueError(f"{who}: start={start!r} outside [0, {S})")
         start = int(start)
@@ -743,7 +776,7 @@ class Prediction_policy:
             raise ValueError(f"{who}: duration={duration!r} outside [1, horizon={H}]")
         D = int(D)
         keep_shift, keep_lat, keep_attn = "shift" in want, "latent_ko" in want, "attention_ko" in want
-        if not (keep_shift or keep_lat or keep_attn):
+        if not (keep_shift or keep_lat or keep_attn or forecast):
             raise ValueError(f"{who}: want={want} asks for nothing")
         Z = self.args.latent_dim if self.args.GAT_use_behavior else 0
         if hist.stride(4) != 1 or hist.stride(3) != d:
@@ -770,6 +803,11 @@ class Prediction_policy:
         # per (environment, job) the knocked chain's outputs
         per_env = 4 * nA * H * (2 * N * (N - 1) + N * A)
         per_job = 4 * nA * H * ((N if keep_shift else 0) + (N * A if keep_lat else 0) + (N * N if keep_attn else 0))
+        if forecast:
+            # the base forecasts (and errors) per environment; per (environment, job) the chain's latents -- a workspace unless they
+            # are a result -- and P floats per pair and step per output, P d with the forecasts themselves
+            per_env += 4 * nA * H * N * P * (d + (1 if keep_err else 0))
+            per_job += 4 * nA * H * ((0 if keep_lat else N * A) + N * P * (2 if keep_err else 1) + (N * P * d if keep_pk else 0))
         budget = int(max_workspace_mb * (1 << 20))
         if budget < per_env + per_job:
             raise ValueError(f"{who}: max_workspace_mb={max_workspace_mb} is too small for one environment and one job "
@@ -784,6 +822,21 @@ class Prediction_policy:
             res["latent_ko"] = torch.empty(nA, E, J, H, N, A, **f32)
         if keep_attn:
             res["attention_ko"] = torch.empty(nA, E, J, H, N, N, **f32)
+        if forecast:
+            res["pred"] = torch.empty(nA, E, H, N, P, d, **f32)
+            res["fshift_sq"] = torch.empty(nA, E, J, H, N, P, **f32)
+            if keep_err:
+                res["ferr_base_sq"] = torch.empty(nA, E, 1, H, N, P, **f32)
+                res["ferr_sq"] = torch.empty(nA, E, J, H, N, P, **f32)
+            if keep_pk:
+                res["pred_ko"] = torch.empty(nA, E, J, H, N, P, d, **f32)
+            # element offset of (agent, env, step start + h, entity 0, feature 0) from the first element of the history view: host
+            # arithmetic, so the bound on what iplan_predict will read is checked here
+            s_net, s_b, s_step, s_ent, _ = src0.stride()
+            row_off = (torch.arange(nA)[:, None, None] * s_net + torch.arange(E)[None, :, None] * s_b +
+                       (start + torch.arange(H))[None, None, :] * s_step).to(torch.int64)
+            assert int(row_off.max()) + (N - 1) * s_ent + d <= ops._room(src0)
+            row_off = row_off.to(dev)
         for e0 in range(0, E, ec):
             e1 = min(E, e0 + ec)
             nz = self._noise(noise, deterministic, nA, e0, e1, (H, N, N - 1, 2), zeros=False)
@@ -792,6 +845,16 @@ class Prediction_policy:
             hc = None if h0 is None else h0[:, e0:e1]
             ops.gat_trace(self.gat_arena, s0[:, :, start:start + H], None if s1 is None else s1[:, :, start:start + H], hc, nz, tau=tau,
                           want=("latent",), out={"latent": base})                  # attention_trace's launch and bits
+            if forecast:
+                nb = e1 - e0
+                pb = ops.predict(self.dec_arena, src0, row_off[:, e0:e1].reshape(nA, nb * H).contiguous(), s_ent, 0,
+                                 base.reshape(nA, nb * H * N, A).contiguous(), N, P, d, checked=True)["pred"]      # predict()'s launch and bits
+                pb = pb.view(nA, nb, H, N, P, d)
+                res["pred"][:, e0:e1] = pb
+                if keep_err:
+                    # the base error in the knocked error's arithmetic: the same kernel on the base walk's latents as its one job
+                    ops.predict_knockout(self.dec_arena, s0, base.unsqueeze(2), start, P, pos=pos, want=("ferr_sq",),
+                                         out={"ferr_sq": res["ferr_base_sq"][:, e0:e1]})
             for j0 in range(0, J, jc):
                 j1 = min(J, j0 + jc)
                 out = {}
@@ -799,10 +862,19 @@ class Prediction_policy:
                     out["shift_sq"] = res["shift_sq"][:, e0:e1, j0:j1]
                 if keep_lat:
                     out["latent_ko"] = res["latent_ko"][:, e0:e1, j0:j1]
+                elif forecast:
+                    out["latent_ko"] = torch.empty(nA, e1 - e0, j1 - j0, H, N, A, **f32)      # the chunk's workspace
                 if keep_attn:
                     out["attn_ko"] = res["attention_ko"][:, e0:e1, j0:j1]
                 ops.gat_knockout_trace(self.gat_arena, s0, s1, hc, jobs[j0:j1], start=start, duration=D, horizon=H,
                                        base=base if keep_shift else None, noise=nz, tau=tau, knock=knock, baseline=rows, want=tuple(out), out=out)
+                if forecast:
+                    fout = {"fshift_sq": res["fshift_sq"][:, e0:e1, j0:j1]}
+                    if keep_err:
+                        fout["ferr_sq"] = res["ferr_sq"][:, e0:e1, j0:j1]
+                    if keep_pk:
+                        fout["pred_ko"] = res["pred_ko"][:, e0:e1, j0:j1]
+                    ops.predict_knockout(self.dec_arena, s0, out["latent_ko"], start, P, pred_base=pb, pos=pos, want=tuple(fout), out=fout)
         final = {"latent": res["latent"].permute(1, 2, 0, 3, 4)}                   # [nA, E, H, ..] -> [E, H, nA, ..]
         jn = np.asarray(jobs, dtype=np.int64)
         if keep_shift:
@@ -812,7 +884,10 @@ class Prediction_policy:
             final["latent_ko"] = res["latent_ko"].permute(1, 3, 0, 2, 4, 5)
         if keep_attn:
             final["attention_ko"] = res["attention_ko"].permute(1, 3, 0, 2, 4, 5)
-        if keep_shift:
+        if forecast:
+            summaries = self._forecast_knockout_results(res, final, src0, jn, start, D, H, P, presence_col, keep_shift, keep_err, keep_pk,
+                                                        shift if keep_shift else None)
+        elif keep_shift:
             # the two means per agent and step: float64 sums and counts per (agent, env, step) formed where the shifts lie (J N times
             # fewer numbers to read back than the shifts), ONE host read-back, the environments added on the host
             win = src0[:, :, start:start + H]
@@ -835,9 +910,67 @@ class Prediction_policy:
         final["knocked"] = jn
         final["sources"] = sources
         final["window"] = (start, D, H)
-        if keep_shift:
+        if forecast:
+            final.update(summaries)
+        elif keep_shift:
             final["summary"] = summary
         return final
+
+    def _forecast_knockout_results(self, res, final, src0, jn, start, D, H, P, presence_col, keep_shift, keep_err, keep_pk, shift):
+        """``attention_knockout_trace(forecast=True)``: the forecast tensors of ``res`` (agent-major, sums of squares) entered into
+        ``final`` in the caller's layout, and every summary of the call after ONE read-back -> dict of host arrays.  ``shift``: the
+        latent shifts [nA,E,J,H,N] where ``summary`` is wanted too."""
+        dev = self.device
+        nA, E, S, N, _ = src0.shape
+        fsh = res["fshift_sq"].sqrt()                                              # [nA, E, J, H, N, P]
+        final["pred"] = res["pred"].permute(1, 2, 0, 3, 4, 5)
+        final["forecast_shift"] = fsh.permute(1, 3, 0, 4, 2, 5)
+        if keep_err:
+            err_b = res["ferr_base_sq"].sqrt()[:, :, 0]                            # [nA, E, H, N, P]
+            err_k = res["ferr_sq"].sqrt()
+            final["forecast_error"] = err_b.permute(1, 2, 0, 3, 4)
+            final["forecast_error_ko"] = err_k.permute(1, 3, 0, 4, 2, 5)
+        if keep_pk:
+            final["pred_ko"] = res["pred_ko"].permute(1, 3, 0, 2, 4, 5, 6)
+        # summary's rule: a pair counts at step h when ego i is present at step start + h and entity j in at least one knocked step
+        there = (src0[..., presence_col] != 0) if presence_col >= 0 else torch.ones(nA, E, S, N, dtype=torch.bool, device=dev)
+        present = there[:, :, start:start + H]
+        jt = torch.as_tensor(jn, device=dev)
+        seen = present[:, :, :D].any(dim=2)[:, :, jt]                              # [nA, E, J]
+        own = jt[:, None] == torch.arange(N, device=dev)[None, :]                  # [J, N]: slot j knocks ego i itself
+        count = present[:, :, None] & seen[:, :, :, None, None]                    # [nA, E, J, H, N]
+        f64 = torch.float64
+        parts = []                                                                 # float64 [nA, E, H, P] each
+        for pick in (~own, own):
+            m = count & pick[None, None, :, None, :]
+            if keep_shift:
+                parts += [torch.where(m, shift, 0.0).sum(dim=(2, 4), dtype=f64)[..., None].expand(nA, E, H, P),
+                          m.sum(dim=(2, 4), dtype=f64)[..., None].expand(nA, E, H, P)]
+            parts += [torch.where(m[..., None], fsh, 0.0).sum(dim=(2, 4), dtype=f64), m.sum(dim=(2, 4), dtype=f64)[..., None].expand(nA, E, H, P)]
+        valid = (start + np.arange(H)[:, None] + 1 + np.arange(P)[None, :]) < S    # [H, P]: the target step is recorded
+        if keep_err:
+            step = torch.as_tensor(np.minimum(start + np.arange(H)[:, None] + 1 + np.arange(P)[None, :], S - 1), device=dev)      # [H, P]
+            target = there[:, :, step] & torch.as_tensor(valid, device=dev)[None, None, :, :, None]      # [nA, E, H, P, N]
+            m = (count & ~own[None, None, :, None, :])[..., None] & target.permute(0, 1, 2, 4, 3)[:, :, None]      # [nA, E, J, H, N, P]
+            parts += [torch.where(m, err_b[:, :, None], 0.0).sum(dim=(2, 4), dtype=f64), torch.where(m, err_k, 0.0).sum(dim=(2, 4), dtype=f64),
+                      m.sum(dim=(2, 4), dtype=f64)]
+        host = torch.stack(parts).cpu().numpy()                                    # [n, nA, E, H, P]: the ONE read-back
+        tot = np.zeros((len(parts), nA, H, P))
+        for e in range(E):                                                         # environment order, whatever the chunks were
+            tot += host[:, :, e]
+        out = {}
+        k = 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if keep_shift:
+                out["summary"] = np.stack([np.where(tot[c + 1] > 0, tot[c] / tot[c + 1], np.nan) for c in (0, 4)], axis=-1)[:, :, 0]
+                k = 2
+            a, b = (k, 2 * k + 2)
+            out["forecast_summary"] = np.stack([np.where(tot[c + 1] > 0, tot[c] / tot[c + 1], np.nan) for c in (a, b)], axis=-1)
+            if keep_err:
+                c = len(parts) - 3
+                out["forecast_error_summary"] = np.stack([np.where(tot[c + 2] > 0, tot[c + i] / tot[c + 2], np.nan) for i in (0, 1)], axis=-1)
+                out["forecast_valid"] = valid
+        return out
 
     # ---------------------------------------------------------------------------- prediction saliency
     def prediction_saliency(self, history_single, attention_hidden, behavior_latent=None, columns=(1, 2), horizons=None, target=None,

@@ -1936,6 +1936,81 @@ def predict(arena, hist, offset, ent_stride, step_stride, h0, N, P, d, want_pred
     return out
 
 
+PREDICT_KNOCKOUT_OUTPUTS = ("fshift_sq", "ferr_sq", "pred_ko")
+
+
+def predict_knockout(arena, history, latent_ko, start, P, pred_base=None, pos=(1, 2), want=("fshift_sq",), out=None, lib=None):
+    """``predict``'s decoder chain run on the latents ``gat_knockout_trace`` wrote, reduced in the kernel to P numbers per row
+    (iplan_predict_knockout), forward only.  history [n_nets,B,S,N,d]: the episode field, a view whose first four dims may be strided
+    arbitrarily, read in place and never knocked -- row (net, b, start + h, i) is the chain's start state, rows start + h + 1 + p its
+    targets.  latent_ko [n_nets,B,J,H,N,32] (first four dims strided, 16-byte aligned rows): the chains' h_0; the window is steps
+    start .. start + H - 1.  ``pos``: up to 16 distinct columns in [0, d), added in the order given.  ``want``: which of fshift_sq
+    [n_nets,B,J,H,N,P] (sum over pos of (pred_ko - pred_base)^2; needs ``pred_base`` [n_nets,B,H,N,P,d], first three dims strided:
+    ``predict``'s forecasts on the walk with nothing knocked, written by an earlier launch), ferr_sq [n_nets,B,J,H,N,P] (the same sum
+    against the recorded future, +0.0 where the target step start + h + 1 + p is not recorded) and pred_ko [n_nets,B,J,H,N,P,d] to
+    produce; ``out``: optional dict of destination views for some of them (the same layouts, first four dims strided).  Everything
+    the kernel will touch is bounds-checked here, on the host.  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res, keep = predict_knockout_args(arena, history, latent_ko, start, P, pred_base, pos, want, out)
+    _launch("predict_knockout_kernel", lambda: lib.call("iplan_predict_knockout", a, L.current_stream(history.device)))
+    res["_args"] = a
+    res["_keep"] = keep
+    return res
+
+
+def predict_knockout_args(arena, history, latent_ko, start, P, pred_base=None, pos=(1, 2), want=("fshift_sq",), out=None):
+    """The descriptor of a ``predict_knockout`` launch, its output tensors and what must stay alive until the launch has been queued,
+    checked but not launched: (IplanPredictKnockoutArgs, dict, list)."""
+    n_nets, B, S, N, d = history.shape
+    A = 32
+    dev = history.device
+    want = tuple(want)
+    assert want and all(k in PREDICT_KNOCKOUT_OUTPUTS for k in want), want
+    assert latent_ko.dim() == 6 and latent_ko.shape[:2] == (n_nets, B) and latent_ko.shape[4:] == (N, A) and latent_ko.device == dev, latent_ko.shape
+    J, H = latent_ko.shape[2:4]
+    start, P = int(start), int(P)
+    assert 1 <= d <= 16 and P >= 1 and J >= 1 and H >= 1 and 1 <= n_nets <= L.MAX_NETS, (d, P, J, H, n_nets)
+    assert 0 <= start and start + H <= S, (start, H, S)
+    assert B * J * H * N <= 0x7fffffff - 16, (B, J, H, N)
+    pos = tuple(int(c) for c in pos)
+    assert 1 <= len(pos) <= 16 and len(set(pos)) == len(pos) and all(0 <= c < d for c in pos), (pos, d)
+    a = L.PredictKnockoutArgs()
+    a.n_nets, a.B, a.J, a.H, a.N, a.P, a.d, a.S, a.start = n_nets, B, J, H, N, P, d, S, start
+    a.n_pos = len(pos)
+    for k, c in enumerate(pos):
+        a.pos[k] = c
+    # the history view: (net, b, step, entity) strided, d contiguous floats per row, every recorded step inside the storage
+    assert history.dtype == torch.float32 and (history.stride(4) == 1 or d == 1), history.stride()
+    hs = history.stride()[:4]
+    assert all(x >= 0 for x in hs), hs
+    _inside(history, sum((history.shape[k] - 1) * hs[k] for k in range(4)) + d, "predict_knockout: history")
+    a.history = history.data_ptr()
+    a.hist_s_net, a.hist_s_b, a.hist_s_step, a.hist_s_ent = hs
+    keep = [history, latent_ko, pred_base]
+    probe = {}
+    _, *ls = _dest_nbjs({"latent_ko": latent_ko}, probe, "latent_ko", (n_nets, B, J, H), (N, A), dev)
+    assert latent_ko.data_ptr() % 16 == 0 and all(x % 4 == 0 for x in ls), ("latent_ko must be 16-byte aligned with strides % 4 == 0", ls)
+    a.latent_ko = latent_ko.data_ptr()
+    a.lat_s_net, a.lat_s_b, a.lat_s_job, a.lat_s_step = ls
+    if pred_base is not None:
+        assert pred_base.shape == (n_nets, B, H, N, P, d) and pred_base.device == dev, pred_base.shape
+        a.pred_base = pred_base.data_ptr()
+        a.pb_s_net, a.pb_s_b, a.pb_s_step = _nbs_strides(pred_base, N * P * d, "pred_base")
+    assert "fshift_sq" not in want or pred_base is not None, "fshift_sq needs pred_base, the forecasts of the window with nothing knocked"
+    a.params, a.params_s_net = arena.data.data_ptr(), arena.net_stride
+    for i, k in enumerate(L.DEC_PARAM_ORDER):
+        a.off[i] = arena.off(k)
+    res = {}
+    pre = {"fshift_sq": "fs", "ferr_sq": "fe", "pred_ko": "pk"}
+    for k in want:
+        inner = (N, P, d) if k == "pred_ko" else (N, P)
+        t, *s = _dest_nbjs(out, res, k, (n_nets, B, J, H), inner, dev)
+        setattr(a, k, t.data_ptr())
+        for name, v in zip(("net", "b", "job", "step"), s):
+            setattr(a, f"{pre[k]}_s_{name}", v)
+    return a, res, keep
+
+
 PDEC_SAL_OUTPUTS = ("state_grad", "latent_grad", "state_l1", "state_gxi", "latent_l1", "latent_gxi", "pred", "active")
 
 

@@ -289,6 +289,109 @@ if "latent_knockout" in set(sys.argv[1:]):
         t = sorted(t)
         print(f"{name:32s} median {t[len(t) // 2]:.3f} ms  min {t[0]:.3f}  max {t[-1]:.3f}  ({len(t)} rounds after 3 warm-up rounds)", flush=True)
 
+if "forecast_knockout" in set(sys.argv[1:]):
+    # forecasts under occlusion through time (iplan_predict_knockout through attention_knockout_trace(forecast=True)) against the route
+    # without it: attention_knockout_trace(want=("latent_ko",)) under the same max_workspace_mb, ops.predict on it in chunks of
+    # environments, the differences and the masked float64 sums in torch, one read-back.  55 entities all knocked, start = 30, D = 1,
+    # H = 20, deterministic; the two alternate in one process, a pair of events around each call; median of 20 after 3 warm-up rounds.
+    from iplan_amd import synth
+    pol = loop.prediction
+    P = args.pred_length
+    S_f, start_f, D_f, H_f, mb_f, pos_f = 50, 30, 1, 20, 256, (1, 2)
+    gen = torch.Generator().manual_seed(5)
+    f_hist = synth.make_history(gen, (E, S_f, nA), N, d, presence_p=0.7).to(dev)
+    f_lat = torch.softmax(torch.randn(E, S_f, nA, N, Z, generator=gen), -1).to(dev)
+    f_hid = (torch.randn(E, nA, N, A, generator=gen) * 0.1).to(dev)
+    f_src = f_hist.permute(2, 0, 1, 3, 4)
+    f_s = f_src.stride()
+    f_off = (torch.arange(nA)[:, None, None] * f_s[0] + torch.arange(E)[None, :, None] * f_s[1] +
+             (start_f + torch.arange(H_f))[None, None, :] * f_s[2]).to(torch.int64).to(dev)      # [nA, E, H]
+
+    def run_new(want=("shift",), mb=mb_f):
+        return pol.attention_knockout_trace(f_hist, f_lat, f_hid, start=start_f, duration=D_f, horizon=H_f, forecast=True, pos=pos_f, want=want,
+                                            max_workspace_mb=mb)
+
+    def run_by_hand(ec=4):
+        r = pol.attention_knockout_trace(f_hist, f_lat, f_hid, start=start_f, duration=D_f, horizon=H_f, want=("latent_ko",), max_workspace_mb=mb_f)
+        lk = r["latent_ko"].permute(2, 0, 3, 1, 4, 5)                                       # [nA, E, J, H, N, A]
+        Jn = lk.shape[2]
+        pb = ops.predict(pol.dec_arena, f_src, f_off.reshape(nA, E * H_f).contiguous(), f_s[3], 0,
+                         r["latent"].permute(2, 0, 1, 3, 4).reshape(nA, E * H_f * N, A).contiguous(), N, P, d, checked=True)["pred"].view(nA, E, H_f, N, P, d)
+        fsh = torch.empty(nA, E, Jn, H_f, N, P, device=dev)
+        for e0 in range(0, E, ec):
+            e1 = min(E, e0 + ec)
+            off = f_off[:, e0:e1, None].expand(nA, e1 - e0, Jn, H_f).reshape(nA, -1).contiguous()
+            pk = ops.predict(pol.dec_arena, f_src, off, f_s[3], 0, lk[:, e0:e1].reshape(nA, (e1 - e0) * Jn * H_f * N, A).contiguous(), N, P, d,
+                             checked=True)["pred"].view(nA, e1 - e0, Jn, H_f, N, P, d)
+            acc = None
+            for c in pos_f:
+                df = pk[..., c] - pb[:, e0:e1, None, ..., c]
+                acc = df * df if acc is None else acc + df * df
+            fsh[:, e0:e1] = acc.sqrt()
+        present = f_src[:, :, start_f:start_f + H_f, :, 0] != 0                             # [nA, E, H, N]
+        seen = present[:, :, :D_f].any(dim=2)                                               # [nA, E, J = N]
+        own = torch.eye(N, dtype=torch.bool, device=dev)
+        count = present[:, :, None] & seen[:, :, :, None, None]
+        parts = []
+        for pick in (~own, own):
+            m = count & pick[None, None, :, None, :]
+            parts += [torch.where(m[..., None], fsh, 0.0).sum(dim=(2, 4), dtype=torch.float64), m.sum(dim=(2, 4), dtype=torch.float64)[..., None].expand(nA, E, H_f, P)]
+        host = torch.stack(parts).cpu().numpy().sum(axis=2)                                 # the one read-back; [4, nA, H, P]
+        return fsh, host
+
+    r_new, (fsh_old, host_old) = run_new(), run_by_hand()
+    fsh_new = r_new["forecast_shift"].permute(2, 0, 4, 1, 3, 5)
+    print("the two routes' forecast_shift bit-equal:", bool(torch.equal(fsh_new.contiguous().view(torch.int32), fsh_old.view(torch.int32))),
+          " largest:", float(fsh_new.max()), " in echo steps:", float(fsh_new[:, :, :, D_f:].max()), flush=True)
+    import numpy as np
+    with np.errstate(divide="ignore", invalid="ignore"):
+        old_mean = host_old[0] / host_old[1]
+    print("largest difference of the two routes' forecast_summary[..., 0]:", float(np.nanmax(np.abs(old_mean - r_new["forecast_summary"][..., 0]))), flush=True)
+    # (the last two rows say where the time goes: without the latent shift and its summary, and without chunking)
+    routes = {"attention_knockout_trace(forecast=True)": run_new, "latent_ko + ops.predict + torch": run_by_hand,
+              "forecast=True, want=()": lambda: run_new(want=()), "forecast=True, want=(), 4096 MB": lambda: run_new(want=(), mb=4096)}
+    times = {name: [] for name in routes}
+    for rnd in range(23):
+        for name, fn in routes.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd >= 3:
+                times[name].append(e0.elapsed_time(e1))
+    # the launches' shares: events around each op's launches in one more call
+    spans, orig = {}, {k: getattr(ops, k) for k in ("gat_trace", "gat_knockout_trace", "predict", "predict_knockout")}
+
+    def timed(k):
+        def call(*a_, **kw_):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            res = orig[k](*a_, **kw_)
+            e1.record()
+            spans.setdefault(k, []).append((e0, e1))
+            return res
+        return call
+    for k in orig:
+        setattr(ops, k, timed(k))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    run_new()
+    e1.record()
+    torch.cuda.synchronize()
+    for k in orig:
+        setattr(ops, k, orig[k])
+    print(f"one call of {e0.elapsed_time(e1):.3f} ms: " + ", ".join(f"{k} {len(v)} launches {sum(a_.elapsed_time(b_) for a_, b_ in v):.3f} ms" for k, v in spans.items()), flush=True)
+    per_env = 4 * nA * H_f * (2 * N * (N - 1) + N * A + N * P * d)
+    per_job = 4 * nA * H_f * (N + N * A + N * P)
+    jc = min(N, (mb_f * 2 ** 20 - per_env) // per_job)
+    ec = min(E, mb_f * 2 ** 20 // (per_env + jc * per_job))
+    print(f"shape: {nA} nets x {E} envs x {N} entities, S = {S_f}, start = {start_f}, D = {D_f}, H = {H_f}, P = {P}; chunks of {ec} envs x {jc} jobs, "
+          f"latent_ko workspace {4 * nA * ec * jc * H_f * N * A / 2 ** 20:.1f} MiB per chunk (the whole latent_ko: {4 * nA * E * N * H_f * N * A / 2 ** 20:.1f} MiB)", flush=True)
+    for name, t in times.items():
+        t = sorted(t)
+        print(f"{name:42s} median {t[len(t) // 2]:.3f} ms  min {t[0]:.3f}  max {t[-1]:.3f}  ({len(t)} rounds after 3 warm-up rounds)", flush=True)
+
 if "gat_phases12" in set(sys.argv[1:]):           # libraries built with -DGAT_P3_CLOCKS only
     clk = torch.zeros(nA * E, 12, dtype=torch.int64, device=dev)
     ops.gat_forward(loop.prediction.gat_arena, hist, lat, hid, noise, out=out, phase_clocks=clk)
