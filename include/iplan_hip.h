@@ -1341,6 +1341,58 @@ typedef struct {
 int iplan_gat_saliency(const IplanGatSaliencyArgs* args, iplan_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Attention saliency through time: iplan_gat_saliency chained over the past steps of the ego's own latent
+ * (csrc/gat_saliency_trace.hip).  `fwd` describes ONE training-form forward launch (its `saved` record filled) over B * R rows per
+ * net: row b * R + r is (env b, record step r), its h_prev the latent of record step r - 1 (the state the chain starts from for
+ * r = 0).  The output GRUCell reads only the ego's own previous latent, so for every target t (record step r = targets[t]), ego i
+ * and lag k = 0 .. min(K, r), with  y_i = <v_i, latent_{r,i}>  and  c_i^(-1) = v_i:
+ *   lag k is iplan_gat_saliency on row r - k with the cotangent c_i^(k-1); its hidden_grad is the carry
+ *   c_i^(k) = d y_i / d latent_{r-k-1,i},   and   G^(k)[i, j, c] = d y_i / d obs_{r-k}[j, c]   (total, through the ego's latent chain).
+ * A lag's arithmetic is iplan_gat_saliency's, statement for statement: a slot's bits are that entry point's bits.
+ * targets: T record steps in [0, R), any order, duplicates allowed; `targets` is the device copy the kernel reads, `targets_host`
+ * the host copy the entry point checks.  v: rows of A floats, (net, b, t, i) at v + net*v_s_net + b*v_s_b + t*v_s_t + i*A.
+ * gate_through: as in IplanGatSaliencyArgs.
+ * Outputs, each optional (NULL = not wanted; at least one is), slot (net, b, t, k) at base + net*s_net + b*s_b + t*s_t + k*s_k,
+ * contiguous inside, k = 0 .. K:
+ *   grad        [N, N, d0 + d1]   G^(k), indexed [ego i, entity j, column]
+ *   pair_gl1    [N, N, n_src]     sum_c |G^(k)[i, j, c]| per source; n_src = 2 if d1 > 0 else 1
+ *   pair_gxi    [N, N, n_src]     sum_c G^(k)[i, j, c] obs_{r-k}[j, c]                 (both share the pair_s_* strides)
+ *   input_grad  [N, d0 + d1]      sum_i G^(k)[i, j, :]: a running fp32 sum over the egos in ascending order, one rounded add each
+ *   carry       [N, A]            c^(k)
+ *   carry_sq    [N]               sum_c c^(k)[i][c]^2: one lane per ego, columns ascending, every product and sum rounded on its own
+ * The slots of lags that do not exist (k > r) are written +0.0 by the kernel: the outputs need no prefill.
+ * scratch (gate_through == 1): at least n_nets * B * T * 2 * N * N * 3H floats, 16-byte aligned; a workgroup reuses its part for
+ * every lag.  One workgroup per (net, b, t) (grid n_nets * B * T), no atomics, no sums across workgroups: a slot's bits depend on
+ * its own operands only -- not on the other targets, scenes or nets, on K, or on which outputs were asked for.  A zero v_i gives
+ * exact zeros at every lag.  2 <= N <= IPLAN_MAX_ENTITIES, d0 >= 1, d1 >= 0, K >= 0.  Parameters, the record and the inputs are
+ * only read.
+ */
+typedef struct {
+    IplanGatFwdArgs fwd;
+    int32_t B, R, T, K;
+    const int32_t* targets;
+    const int32_t* targets_host;
+    const float* v;
+    int64_t v_s_net, v_s_b, v_s_t;
+    int32_t gate_through;
+    float* scratch;
+    int64_t scratch_floats;
+    float* grad;
+    int64_t grad_s_net, grad_s_b, grad_s_t, grad_s_k;
+    float* pair_gl1;
+    float* pair_gxi;
+    int64_t pair_s_net, pair_s_b, pair_s_t, pair_s_k;
+    float* input_grad;
+    int64_t ig_s_net, ig_s_b, ig_s_t, ig_s_k;
+    float* carry;
+    int64_t carry_s_net, carry_s_b, carry_s_t, carry_s_k;
+    float* carry_sq;
+    int64_t csq_s_net, csq_s_b, csq_s_t, csq_s_k;
+} IplanGatSaliencyTraceArgs;
+
+int iplan_gat_saliency_trace(const IplanGatSaliencyTraceArgs* args, iplan_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Prediction saliency: the input Jacobian of the chain iplan_predict walks (csrc/pdec_saliency.hip),
  *   x_0 = start state, h_{-1} = h0;  t < P:  u_t = ReLU(W_lin x_t + b_lin), h_t = GRU32(u_t, h_{t-1}), y_t = W_out tanh(h_t) + b_out, x_{t+1} = y_t
  * (Prediction_Decoder.forward(last_state, None, hidden) under .eval(): no teacher forcing, no dropout).  Rows, the start state read in

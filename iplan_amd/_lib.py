@@ -55,7 +55,8 @@ ENTRY_POINTS = ["iplan_gat_fwd", "iplan_enc_fwd", "iplan_ac_fwd", "iplan_adam_st
                 "iplan_p2p_publish", "iplan_p2p_reduce", "iplan_obs_history_step", "iplan_seq2seq_bwd", "iplan_predict", "iplan_beh_eval",
                 "iplan_gat_trace", "iplan_ac_trace", "iplan_ppo_eval", "iplan_ac_saliency", "iplan_ac_saliency_lag", "iplan_enc_saliency",
                 "iplan_gat_saliency", "iplan_pdec_saliency", "iplan_gat_knockout", "iplan_ac_knockout", "iplan_ac_knockout_trace",
-                "iplan_gat_knockout_trace", "iplan_ac_knockout_chain", "iplan_enc_knockout", "iplan_predict_knockout"]
+                "iplan_gat_knockout_trace", "iplan_ac_knockout_chain", "iplan_enc_knockout", "iplan_predict_knockout",
+                "iplan_gat_saliency_trace"]
 RAW_ENTRY_POINTS = ["iplan_grad_sqnorm", "iplan_wgrad_workspace_floats", "iplan_ac_kpad", "iplan_ac_fc1_groups", "iplan_sizeof", "iplan_ac_packed_floats",
                     "iplan_p2p_alloc", "iplan_p2p_free", "iplan_p2p_export", "iplan_p2p_open", "iplan_p2p_close", "iplan_gat_enc_fwd", "iplan_gat_enc_ac_fwd", "iplan_gumbel_noise", "iplan_ac_xhat_floats", "iplan_ac_fc1_split_chunks", "iplan_ac_fc1_split_parts",
                     "iplan_ppo_eval_workspace_bytes"]      # non (args*, stream) signatures
@@ -471,6 +472,19 @@ class GatSaliencyArgs(C.Structure):
     ]
 
 
+class GatSaliencyTraceArgs(C.Structure):
+    _fields_ = [
+        ("fwd", GatFwdArgs), ("B", i32), ("R", i32), ("T", i32), ("K", i32), ("targets", fp), ("targets_host", fp),
+        ("v", fp), ("v_s_net", i64), ("v_s_b", i64), ("v_s_t", i64), ("gate_through", i32),
+        ("scratch", fp), ("scratch_floats", i64),
+        ("grad", fp), ("grad_s_net", i64), ("grad_s_b", i64), ("grad_s_t", i64), ("grad_s_k", i64),
+        ("pair_gl1", fp), ("pair_gxi", fp), ("pair_s_net", i64), ("pair_s_b", i64), ("pair_s_t", i64), ("pair_s_k", i64),
+        ("input_grad", fp), ("ig_s_net", i64), ("ig_s_b", i64), ("ig_s_t", i64), ("ig_s_k", i64),
+        ("carry", fp), ("carry_s_net", i64), ("carry_s_b", i64), ("carry_s_t", i64), ("carry_s_k", i64),
+        ("carry_sq", fp), ("csq_s_net", i64), ("csq_s_b", i64), ("csq_s_t", i64), ("csq_s_k", i64),
+    ]
+
+
 class GatKnockoutArgs(C.Structure):
     _fields_ = [
         ("n_nets", i32), ("B", i32), ("N", i32), ("d0", i32), ("d1", i32), ("J", i32),
@@ -638,4 +652,5 @@ STRUCT_MIRRORS = {"IplanGatSaved": GatSaved, "IplanGatFwdArgs": GatFwdArgs, "Ipl
                   "IplanPdecSaliencyArgs": PdecSaliencyArgs, "IplanGatKnockoutArgs": GatKnockoutArgs,
                   "IplanAcKnockoutArgs": AcKnockoutArgs, "IplanAcKnockoutTraceArgs": AcKnockoutTraceArgs,
                   "IplanGatKnockoutTraceArgs": GatKnockoutTraceArgs, "IplanAcKnockoutChainArgs": AcKnockoutChainArgs,
-                  "IplanEncKnockoutArgs": EncKnockoutArgs, "IplanPredictKnockoutArgs": PredictKnockoutArgs}
+                  "IplanEncKnockoutArgs": EncKnockoutArgs, "IplanPredictKnockoutArgs": PredictKnockoutArgs,
+                  "IplanGatSaliencyTraceArgs": GatSaliencyTraceArgs}

@@ -29,7 +29,7 @@ extern "C" size_t iplan_sizeof(const char* name) {
     IPLAN_SZ(IplanAcSaliencyArgs) IPLAN_SZ(IplanAcSaliencyLagArgs) IPLAN_SZ(IplanEncSaliencyArgs) IPLAN_SZ(IplanGatSaliencyArgs)
     IPLAN_SZ(IplanPdecSaliencyArgs) IPLAN_SZ(IplanGatKnockoutArgs) IPLAN_SZ(IplanAcKnockoutArgs)
     IPLAN_SZ(IplanAcKnockoutTraceArgs) IPLAN_SZ(IplanGatKnockoutTraceArgs) IPLAN_SZ(IplanAcKnockoutChainArgs)
-    IPLAN_SZ(IplanEncKnockoutArgs) IPLAN_SZ(IplanPredictKnockoutArgs)
+    IPLAN_SZ(IplanEncKnockoutArgs) IPLAN_SZ(IplanPredictKnockoutArgs) IPLAN_SZ(IplanGatSaliencyTraceArgs)
 #undef IPLAN_SZ
     return 0;
 }

@@ -19,6 +19,11 @@
 //      grad, the two pair maps, and input_grad[j] = sum_i G[i, j, :] -- a running fp32 sum in registers, one plain add per ego.
 // No atomics and no sums across scenes: a scene's bits depend on nothing but its own operands -- not on its workgroup, the other
 // scenes, or on which outputs were asked for.
+//
+// RESTATED in gat_saliency_trace.hip: its lag loop holds the phases A, B, D, P below statement for statement, and its slots are
+// tested to be this kernel's bits.  A change to the arithmetic here has to be made there too.  What differs there on purpose: the
+// cotangent comes from an LDS table and the hidden gradient is always formed (it is the next lag's cotangent), the parameter pointer
+// is made opaque once per lag as well, and phase P's per-source pair sums are scalars (the indexed pair went to scratch memory there).
 #include "api_util.h"
 #include "gru_tile.h"
 

@@ -27,6 +27,23 @@ def _as_dev(x, device):
     return x.to(device=device, dtype=torch.float32)
 
 
+def _halving_sum(x, dim):
+    """sum over ``dim`` in a fixed order any host can restate: the axis is zero-padded to a power of two, then its upper half is
+    added to its lower half, elementwise, until one entry is left"""
+    n = x.shape[dim]
+    size = 1
+    while size < n:
+        size *= 2
+    if size > n:
+        pad = list(x.shape)
+        pad[dim] = size - n
+        x = torch.cat([x, torch.zeros(pad, dtype=x.dtype, device=x.device)], dim=dim)
+    while size > 1:
+        size //= 2
+        x = x.narrow(dim, 0, size) + x.narrow(dim, size, size)
+    return x.squeeze(dim)
+
+
 class Prediction_policy:
     def __init__(self, args, logger):
         self.device = torch.device("cuda" if args.use_cuda else "cpu")
@@ -469,6 +486,236 @@ class Prediction_policy:
         res["active_h"], res["active_v"] = act_h, act_v
         res = {k: v.unflatten(1, (E, S)).permute(1, 2, 0, *range(3, v.dim() + 1)) for k, v in res.items()}
         return {k: v.cpu().numpy() for k, v in res.items()} if as_np else res
+
+    # ---------------------------------------------------------------------------- attention saliency through time
+    def _gat_saliency_trace_plan(self, who, N, S, targets, K, through, deterministic, max_workspace_mb):
+        """How ``attention_saliency_trace`` splits its work -> (environments per chunk, [(first, last + 1) target positions of each
+        run]).  A chunk holds, per environment and agent, the training-form record and the noise of the steps its run of targets
+        reaches, one scratch scene per target and (when the noise is sampled) the walk's noise over all S steps; that stays under
+        ``max_workspace_mb``.  All targets in one run if at least one environment fits that way (then as many environments as
+        fit); otherwise one environment per chunk and the targets in greedy runs."""
+        nA, A = self.n_agents, self.args.attention_dim
+        row = 2 * ((N + 15) // 16) * (N - 1) * 2048 + N * (8 * A + 2 * (N - 1)) + 2 * N * (N - 1)      # record + noise of one step
+        scene = ops.gat_saliency_trace_scratch_floats(1, 1, 1, N) if through else 0
+        walk = 0 if deterministic else S * 2 * N * (N - 1)
+
+        def per_env(t0, t1):
+            return 4 * nA * ((targets[t1 - 1] - max(0, targets[t0] - K) + 1) * row + (t1 - t0) * scene + walk)
+        budget = int(max_workspace_mb * (1 << 20))
+        T = len(targets)
+        worst = max(per_env(t, t + 1) for t in range(T))
+        if worst > budget:
+            raise ValueError(f"{who}: max_workspace_mb={max_workspace_mb} is too small for one environment and one target with its "
+                             f"{min(K, max(targets)) + 1}-step record ({worst / (1 << 20):.1f} MB)")
+        if per_env(0, T) <= budget:
+            return budget // per_env(0, T), [(0, T)]
+        runs, t0 = [], 0
+        while t0 < T:
+            t1 = t0 + 1
+            while t1 < T and per_env(t0, t1 + 1) <= budget:
+                t1 += 1
+            runs.append((t0, t1))
+            t0 = t1
+        return 1, runs
+
+    def attention_saliency_trace(self, history, behavior_latent=None, hidden0=None, lags=0, targets=None, target="self", noise=None,
+                                 deterministic=True, gate="through", tau=None, want=("pair",), presence_col=0, max_workspace_mb=256):
+        """Ego i's social context at step s -- how much of it is owed to what vehicle j did k steps ago?  ``attention_saliency``
+        through time.  The chain is ``attention_trace``'s: latent_s = GAT([history_s || behavior_latent_s], latent_{s-1}),
+        latent_{-1} = ``hidden0`` [E,nA,N,A] (None: zeros), over ``history`` [E,S,nA,N,d] (with ``behavior_latent`` [E,S,nA,N,Z];
+        needed with ``GAT_use_behavior``, ignored without).  For every target step s of ``targets`` (None: every step; else an
+        ascending list of distinct steps -- the output axis T), ego i and lag k = 0 .. ``lags`` (an int in [0, S-1]):
+            y_{s,i} = <v_{s,i}, latent_{s,i}>,   G^(k)[i, j, c] = d y_{s,i} / d obs_{s-k}[j, c],   c^(k)[i] = d y_{s,i} / d latent_{s-k-1,i}
+        -- total derivatives through the ego's own latent chain (the output cell reads no other entity's latent, so there is no
+        other path through time); for k = s the carry c^(k) is d y / d hidden0.  Lags with s - k < 0 do not exist: their slots
+        are +0.0 and ``lag_valid`` is False.
+        ``target``: "self" -> v = latent_s; an int -> the one-hot of that unit; a tensor [E,T,nA,N,A] -> used as given (e.g. the
+        ``att`` columns of ``DcntrlMAC.saliency``'s ``actor_input_grad`` at the target steps).  ``deterministic``, ``noise``
+        [nA,E,S,N,N-1,2], ``gate`` and ``tau`` as in ``attention_saliency``.
+        Returns a dict, pair tensors indexed [ego i, entity j], n_src = 2 with ``GAT_use_behavior`` else 1:
+          ``pair_gl1``, ``pair_gxi`` [E,T,K+1,nA,N,N,n_src]   per lag, as ``attention_saliency`` defines them ("pair" in ``want``)
+          ``grad`` [E,T,K+1,nA,N,N,d+Z]                       all of G^(k) ("grad" in ``want``)
+          ``input_grad`` [E,T,K+1,nA,N,d+Z]                   sum_i G^(k)[i,j,:]
+          ``carry_l2`` [E,T,K+1,nA,N]                         |c^(k)[i]|;  ``carry`` [E,T,K+1,nA,N,A] with "carry" in ``want``
+          ``lag_valid`` [T,K+1] bool, ``targets`` [T], ``target_vector`` [E,T,nA,N,A], ``latent`` [E,S,nA,N,A] (``attention_trace``'s bits)
+          ``active_h``, ``active_v`` [E,S,nA,N,32] bool       the ReLU branches the backward used (False at steps no target reaches)
+          ``lag_l1`` [nA,K+1,n_src,2] float64, ``lag_pairs`` [nA,K+1,2]  ("pair" in ``want``) per lag the mean of ``pair_gl1`` over the
+                                                              counting pairs and their number, split into (i != j, i == j): "how far
+                                                              back does the social context look".  A pair counts when the lag exists,
+                                                              ego i is present at step s and entity j at step s - k (column
+                                                              ``presence_col`` of its history row non-zero; < 0: everything counts);
+                                                              nothing counting gives NaN.  Summed in float64 per environment from the
+                                                              outputs in a stated order (entities, then egos, then targets, each axis
+                                                              by pairwise halving), ONE read-back, environments added in order: a host
+                                                              restatement of that order gives the same bits.
+        Per chunk (a group of environments times a run of targets, see ``max_workspace_mb``): one ``iplan_gat_trace`` walk per
+        group of environments, one training-form forward over the steps the run reaches with the walk's cat(hidden0, latent[:-1])
+        as its previous state -- formed once, read by every target and lag -- and one ``iplan_gat_saliency_trace`` launch.  A
+        slot's bits do not depend on the chunking, the other targets, ``lags`` or ``want``.  ``max_workspace_mb``: the default is small for
+        many entities -- near N = 55 one environment's record of lags + 1 steps nearly fills it, a chunk is then one environment and a
+        target or two, its few workgroups walk their lags in series, and the call is slower than lags + 1 ``attention_saliency`` calls
+        (profiles/r30_attention_saliency_trace_notes.md); raise it (e.g. 8192) where the memory is there.  numpy in -> numpy out.  Parameters,
+        gradients, optimiser state and (with ``deterministic=True``) torch's generator are not touched."""
+        who = "attention_saliency_trace"
+        as_np = isinstance(history, np.ndarray)
+        dev = self.device
+        hist = _as_dev(history, dev)
+        if hist.dim() != 5:
+            raise ValueError(f"{who}: history must be [E,S,nA,N,d], got {tuple(hist.shape)}")
+        E, S, nA, N, d = hist.shape
+        A = self.args.attention_dim
+        if nA != self.n_agents or d != self.obs_shape or not 2 <= N <= ops.L.GAT_MAX_ENTITIES or E < 1 or S < 1:
+            raise ValueError(f"{who}: history {tuple(hist.shape)} does not fit n_agents={self.n_agents}, obs width {self.obs_shape}, "
+                             f"2 <= N <= {ops.L.GAT_MAX_ENTITIES}")
+        if gate not in ("through", "held"):
+            raise ValueError(f"{who}: gate={gate!r} is neither 'through' nor 'held'")
+        want = tuple(want)
+        if any(k not in ("pair", "grad", "carry") for k in want):
+            raise ValueError(f"{who}: want={want} -- known: 'pair', 'grad', 'carry'")
+        if deterministic and noise is not None:
+            raise ValueError(f"{who}: noise was given together with deterministic=True")
+        tau = 0.01 if tau is None else float(tau)
+        if not tau > 0:
+            raise ValueError(f"{who}: tau={tau} must be positive")
+        if isinstance(lags, bool) or not isinstance(lags, (int, np.integer)) or not 0 <= int(lags) <= S - 1:
+            raise ValueError(f"{who}: lags={lags!r} must be an int in [0, S-1={S - 1}]")
+        K = int(lags)
+        if targets is None:
+            tg = list(range(S))
+        else:
+            given = list(targets)                                                 # (read once: a generator would be spent after it)
+            ok = bool(given) and all(isinstance(t, (int, np.integer)) and not isinstance(t, bool) and 0 <= t < S for t in given)
+            if not ok or any(b <= a for a, b in zip(given, given[1:])):
+                raise ValueError(f"{who}: targets={given} must be an ascending list of distinct steps in [0, {S})")
+            tg = [int(t) for t in given]
+        T = len(tg)
+        if isinstance(presence_col, bool) or not isinstance(presence_col, (int, np.integer)) or presence_col >= d:
+            raise ValueError(f"{who}: presence_col={presence_col!r} must be an int below the history's {d} columns (< 0: everything counts)")
+        Z = self.args.latent_dim if self.args.GAT_use_behavior else 0
+        lat = self._beh_latent(who, behavior_latent, (E, S, nA, N, Z))
+        if lat is not None:
+            lat = lat.permute(2, 0, 1, 3, 4)
+        D, n_src = d + Z, 2 if Z else 1
+        if hist.stride(4) != 1 or hist.stride(3) != d:
+            hist = hist.contiguous()
+        src0 = hist.permute(2, 0, 1, 3, 4)                                        # [nA, E, S, N, d] view
+        f32 = dict(dtype=torch.float32, device=dev)
+        if hidden0 is None:
+            h0 = torch.zeros(nA, E, N, A, **f32)
+        else:
+            h0 = _as_dev(hidden0, dev)
+            if h0.shape != (E, nA, N, A):
+                raise ValueError(f"{who}: hidden0 {tuple(h0.shape)} != {(E, nA, N, A)}")
+            h0 = h0.permute(1, 0, 2, 3).contiguous()
+        if noise is not None:
+            noise = _as_dev(noise, dev)
+            if noise.shape != (nA, E, S, N, N - 1, 2):
+                raise ValueError(f"{who}: noise {tuple(noise.shape)} != {(nA, E, S, N, N - 1, 2)}")
+        vt = None
+        if isinstance(target, str):
+            if target != "self":
+                raise ValueError(f"{who}: target={target!r} -- 'self', a unit index or a tensor [E,T,nA,N,A]")
+        elif isinstance(target, (int, np.integer)) and not isinstance(target, bool):
+            if not 0 <= int(target) < A:
+                raise ValueError(f"{who}: target unit {target} outside [0, {A})")
+            vt = torch.zeros(nA, E, T, N, A, **f32)
+            vt[..., int(target)] = 1.0
+        elif isinstance(target, (np.ndarray, torch.Tensor)):
+            vt = _as_dev(target, dev)
+            if vt.shape != (E, T, nA, N, A):
+                raise ValueError(f"{who}: target {tuple(vt.shape)} != {(E, T, nA, N, A)}")
+            vt = vt.permute(2, 0, 1, 3, 4).contiguous()
+        else:
+            raise ValueError(f"{who}: target={target!r} -- 'self', a unit index or a tensor [E,T,nA,N,A]")
+        through = gate == "through"
+        e_chunk, runs = self._gat_saliency_trace_plan(who, N, S, tg, K, through, deterministic, max_workspace_mb)
+
+        latent = torch.empty(E, S, nA, N, A, **f32)
+        lat_w = latent.permute(2, 0, 1, 3, 4)                                     # [nA, E, S, N, A] view the walk writes
+        outs = {"input_grad": torch.empty(nA, E, T, K + 1, N, D, **f32), "carry_sq": torch.empty(nA, E, T, K + 1, N, **f32)}
+        if "pair" in want:
+            outs["pair_gl1"] = torch.empty(nA, E, T, K + 1, N, N, n_src, **f32)
+            outs["pair_gxi"] = torch.empty(nA, E, T, K + 1, N, N, n_src, **f32)
+        if "grad" in want:
+            outs["grad"] = torch.empty(nA, E, T, K + 1, N, N, D, **f32)
+        if "carry" in want:
+            outs["carry"] = torch.empty(nA, E, T, K + 1, N, A, **f32)
+        if vt is None:
+            vt = torch.empty(nA, E, T, N, A, **f32)
+            self_target = True
+        else:
+            self_target = False
+        act_h = torch.zeros(nA, E, S, N, A, dtype=torch.bool, device=dev)
+        act_v = torch.zeros(nA, E, S, N, A, dtype=torch.bool, device=dev)
+        # a run's targets as record steps, on the device: the same for every group of environments, uploaded once
+        run_tg = [[s - max(0, tg[t0] - K) for s in tg[t0:t1]] for t0, t1 in runs]
+        run_dev = [torch.tensor(r, dtype=torch.int32, device=dev) for r in run_tg]
+        for e0 in range(0, E, e_chunk):
+            e1 = min(E, e0 + e_chunk)
+            Ee = e1 - e0
+            nz = self._noise(noise, deterministic, nA, e0, e1, (S, N, N - 1, 2), zeros=False)
+            ops.gat_trace(self.gat_arena, src0[:, e0:e1], None if lat is None else lat[:, e0:e1], h0[:, e0:e1], nz, tau=tau,
+                          want=("latent",), out={"latent": lat_w[:, e0:e1]})
+            if self_target:
+                vt[:, e0:e1] = lat_w[:, e0:e1, tg]
+            for run, (t0, t1) in enumerate(runs):
+                r0, r1 = max(0, tg[t0] - K), tg[t1 - 1] + 1                       # the record's steps r0 .. r1 - 1
+                R = r1 - r0
+                rows = lambda x: x[:, e0:e1, r0:r1].reshape(nA, Ee * R, *x.shape[3:])     # noqa: E731  (env, step) rows: data movement only
+                if r0 == 0:
+                    hprev = torch.cat([h0[:, e0:e1].unsqueeze(2), lat_w[:, e0:e1, :r1 - 1]], dim=2).reshape(nA, Ee * R, N, A)
+                else:
+                    hprev = lat_w[:, e0:e1, r0 - 1:r1 - 1].reshape(nA, Ee * R, N, A)
+                nzr = torch.zeros(nA, Ee * R, N, N - 1, 2, **f32) if deterministic else nz[:, :, r0:r1].reshape(nA, Ee * R, N, N - 1, 2).contiguous()
+                _, saved = ops.gat_forward(self.gat_arena, rows(src0).contiguous(), None if lat is None else rows(lat).contiguous(),
+                                           hprev.contiguous(), nzr, tau=tau, save=True)
+                ops.gat_saliency_trace(self.gat_arena, saved, R, vt[:, e0:e1, t0:t1], run_tg[run], K, gate_through=through, want=tuple(outs),
+                                       out={k: t[:, e0:e1, t0:t1] for k, t in outs.items()}, targets_dev=run_dev[run])
+                act_h[:, e0:e1, r0:r1] = saved["h_enc"].view(nA, Ee, R, N, A) > 0
+                act_v[:, e0:e1, r0:r1] = saved["qkv"].view(nA, Ee, R, N, 3 * A)[..., 2 * A:] > 0
+                del saved                                                         # (not held while the next chunk's record is formed)
+        tgt = torch.tensor(tg, dtype=torch.int64)
+        lag_valid = torch.arange(K + 1)[None, :] <= tgt[:, None]                   # [T, K+1]
+        sums = None
+        if "pair" in want:
+            # per environment, in float64 where the outputs lie: the sums of pair_gl1 and the counts over the counting pairs
+            step_j = (tgt[:, None] - torch.arange(K + 1)[None, :]).clamp(min=0).to(dev)
+            tgt_d, valid_d = tgt.to(dev), lag_valid.to(dev)
+            eye = torch.eye(N, dtype=torch.bool, device=dev)
+            parts = []
+            for e in range(E):
+                if presence_col >= 0:
+                    pres = src0[:, e, :, :, presence_col] != 0                    # [nA, S, N]
+                    m = pres[:, tgt_d][:, :, None, :, None] & pres[:, step_j][:, :, :, None, :]
+                else:
+                    m = torch.ones(nA, T, K + 1, N, N, dtype=torch.bool, device=dev)
+                m = m & valid_d[None, :, :, None, None]
+                g = outs["pair_gl1"][:, e].to(torch.float64)                      # [nA, T, K+1, N, N, n_src]
+                split = [m & ~eye, m & eye]
+                # in a stated order -- entities, then egos, then targets, each by pairwise halving -- so that a host restatement
+                # of the same order gives the same bits (counts are integers: any order)
+                tot = torch.stack([_halving_sum(_halving_sum(_halving_sum(g * s[..., None], 4), 3), 1) for s in split], dim=-1)   # [nA, K+1, n_src, 2]
+                cnt = torch.stack([s.sum(dim=(1, 3, 4)).to(torch.float64) for s in split], dim=-1)                # [nA, K+1, 2]
+                parts.append(torch.cat([tot, cnt[:, :, None, :]], dim=2))         # [nA, K+1, n_src + 1, 2]
+            sums = torch.stack(parts)
+        res = {k: v.permute(1, 2, 3, 0, *range(4, v.dim())) for k, v in outs.items()}
+        res["carry_l2"] = torch.sqrt(res.pop("carry_sq"))
+        res["latent"] = latent
+        res["target_vector"] = vt.permute(1, 2, 0, 3, 4)
+        res["active_h"], res["active_v"] = act_h.permute(1, 2, 0, 3, 4), act_v.permute(1, 2, 0, 3, 4)
+        res["lag_valid"], res["targets"] = lag_valid, tgt
+        if as_np:
+            res = {k: v.cpu().numpy() for k, v in res.items()}
+        if sums is not None:
+            m = sums.cpu().numpy()                                                # ONE host read-back
+            tot = np.zeros(m.shape[1:])
+            for e in range(E):                                                    # environment order, whatever the chunks were
+                tot += m[e]
+            cnt = tot[:, :, n_src, :]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                res["lag_l1"] = np.where(cnt[:, :, None, :] > 0, tot[:, :, :n_src, :] / cnt[:, :, None, :], np.nan)
+            res["lag_pairs"] = cnt
+        return res
 
     # ---------------------------------------------------------------------------- neighbour knock-out
     def _knock_spec(self, who, N, d, sources, want, noise, deterministic, tau, presence_col, entities, baseline):

@@ -464,6 +464,92 @@ def gat_saliency_args(arena, saved, v, gate_through=True, want=("input_grad",), 
     return a, res, keep
 
 
+GAT_SALIENCY_TRACE_OUTPUTS = ("grad", "pair_gl1", "pair_gxi", "input_grad", "carry", "carry_sq")
+
+
+def gat_saliency_trace_scratch_floats(n_nets, B, T, N):
+    """floats of scratch an exact-gate ``gat_saliency_trace`` launch needs: one ``gat_saliency`` scene's worth per (net, env, target),
+    reused by every lag"""
+    return n_nets * B * T * 2 * N * N * 3 * 32
+
+
+def gat_saliency_trace(arena, saved, steps, v, targets, lags=0, gate_through=True, want=("input_grad",), out=None, scratch=None, targets_dev=None,
+                       lib=None):
+    """``gat_saliency`` chained over the past steps of each ego's own latent (iplan_gat_saliency_trace).  ``saved``: what ONE
+    ``gat_forward(..., save=True)`` over rows (env, record step) returned -- B * ``steps`` rows per net, row b * steps + r, its
+    ``h_prev`` row the latent of record step r - 1; it is read in place by every target and lag that reaches a row.  ``targets``:
+    T record steps in [0, steps); ``lags`` = K >= 0; v [n_nets,B,T,N,A] (first three dims strided): the cotangent of every target.
+    For lag k <= min(K, r) the slot holds ``gat_saliency`` on row r - k with the previous lag's ``hidden_grad`` as cotangent (bit for
+    bit); the slots of lags k > r are +0.0.  ``want``: which of grad [n_nets,B,T,K+1,N,N,D], pair_gl1 / pair_gxi
+    [n_nets,B,T,K+1,N,N,n_src], input_grad [n_nets,B,T,K+1,N,D], carry [n_nets,B,T,K+1,N,A] (the lag's hidden gradient), carry_sq
+    [n_nets,B,T,K+1,N] (its squared norm) to produce; ``out``: optional dict of destination views for some of them (first four dims
+    strided, inside their storage); ``scratch``: optional float32 buffer of at least ``gat_saliency_trace_scratch_floats`` floats;
+    ``targets_dev``: optional int32 device tensor already holding ``targets`` (a caller that launches the same list many times uploads
+    it once; the host list is still what the entry point checks).  Returns a dict of the wanted tensors."""
+    lib = _lib(lib)
+    a, res, keep = gat_saliency_trace_args(arena, saved, steps, v, targets, lags, gate_through, want, out, scratch, targets_dev)
+    _launch("gat_saliency_trace_kernel", lambda: lib.call("iplan_gat_saliency_trace", a, L.current_stream(v.device)))
+    res["_keep"] = keep
+    return res
+
+
+def gat_saliency_trace_args(arena, saved, steps, v, targets, lags=0, gate_through=True, want=("input_grad",), out=None, scratch=None,
+                            targets_dev=None):
+    """The descriptor of a ``gat_saliency_trace`` launch, its output tensors and what must stay alive until the launch has been
+    queued, checked but not launched: (IplanGatSaliencyTraceArgs, dict, list)."""
+    fa = saved["_args"]
+    n_nets, rows, N, d0, d1 = fa.n_nets, fa.B, fa.N, fa.d0, fa.d1
+    R, K = int(steps), int(lags)
+    assert R >= 1 and rows % R == 0, (rows, R)
+    B = rows // R
+    A, D, n_src = 32, d0 + d1, 2 if d1 > 0 else 1
+    dev = v.device
+    want = tuple(want)
+    assert want and all(k in GAT_SALIENCY_TRACE_OUTPUTS for k in want), want
+    assert fa.params == arena.data.data_ptr(), "saved belongs to another arena"
+    assert K >= 0, K
+    targets = [int(t) for t in targets]
+    T = len(targets)
+    assert T >= 1 and all(0 <= t < R for t in targets), (targets, R)
+    a = L.GatSaliencyTraceArgs()
+    a.fwd = fa
+    a.B, a.R, a.T, a.K = B, R, T, K
+    t_host = (C.c_int32 * T)(*targets)
+    if targets_dev is None:
+        t_dev = torch.tensor(targets, dtype=torch.int32, device=dev)
+    else:
+        t_dev = targets_dev
+        assert t_dev.shape == (T,) and t_dev.dtype == torch.int32 and t_dev.is_contiguous() and t_dev.device == dev, (t_dev.shape, t_dev.dtype)
+    a.targets, a.targets_host = t_dev.data_ptr(), C.cast(t_host, C.c_void_p)
+    assert v.shape == (n_nets, B, T, N, A) and v.dtype == torch.float32, (v.shape, v.dtype)
+    a.v = v.data_ptr()
+    a.v_s_net, a.v_s_b, a.v_s_t = _nbs_strides(v, N * A, "v")
+    a.gate_through = 1 if gate_through else 0
+    keep = [saved, v, t_host, t_dev]
+    if gate_through:
+        need = gat_saliency_trace_scratch_floats(n_nets, B, T, N)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.float32, device=dev)
+        assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= need and scratch.device == dev, (scratch.numel(), need)
+        a.scratch, a.scratch_floats = scratch.data_ptr(), scratch.numel()
+        keep.append(scratch)
+    res = {}
+    inner = {"grad": (N, N, D), "pair_gl1": (N, N, n_src), "pair_gxi": (N, N, n_src), "input_grad": (N, D), "carry": (N, A), "carry_sq": (N,)}
+    pre = {"grad": "grad", "input_grad": "ig", "carry": "carry", "carry_sq": "csq"}
+    pair = None
+    for k in want:
+        t, *s = _dest_nbjs(out, res, k, (n_nets, B, T, K + 1), inner[k], dev)
+        setattr(a, k, t.data_ptr())
+        if k in pre:
+            for name, x in zip(("net", "b", "t", "k"), s):
+                setattr(a, f"{pre[k]}_s_{name}", x)
+        else:
+            assert pair is None or pair == tuple(s), "pair_gl1 and pair_gxi share their strides"
+            pair = tuple(s)
+            a.pair_s_net, a.pair_s_b, a.pair_s_t, a.pair_s_k = s
+    return a, res, keep
+
+
 _FUSED_SYNC = {}
 
 
