@@ -504,8 +504,8 @@ int iplan_ppo_prepare(const IplanPpoPrepareArgs* args, iplan_stream_t stream);
  *   phase 2:  adv[net, i] = (adv[net, i] - mean) / (sqrt(sqdev[net] / (count - 1)) + 1e-5)
  * count = rows of all ranks.  With one rank this reproduces iplan_ppo_prepare's own normalisation.                    */
 typedef struct {
-    int32_t n_agents, n;         /* n = this rank's rows per agent                                   */
-    int64_t row_stride;          /* per-agent stride of adv                                          */
+    int32_t n_agents, n;         /* n = this rank's rows per agent; 1 <= n <= row_stride (refused otherwise) */
+    int64_t row_stride;          /* per-agent stride of adv; entries [n, row_stride) are left alone  */
     float* adv;                  /* [n_agents, row_stride]                                           */
     float* sum;                  /* [n_agents]                                                       */
     float* sqdev;                /* [n_agents]                                                       */
@@ -519,8 +519,9 @@ int iplan_ppo_adv_norm(const IplanAdvNormArgs* args, iplan_stream_t stream);
  * `rows` rows of every agent, plus dLoss/dlogp and d(value_loss_coef * value_loss)/dvalue per row.
  * stats[net][0..4] = policy_loss, value_loss, mean ratio, mean entropy, sum(mask).              */
 typedef struct {
-    int32_t n_agents, rows;
-    int64_t row_stride;          /* per-agent stride of the [n_agents, bs*T] inputs below            */
+    int32_t n_agents, rows;      /* 1 <= rows <= row_stride (refused otherwise)                      */
+    int64_t row_stride;          /* per-agent stride of the [n_agents, bs*T] inputs below; their entries
+                                    [rows, row_stride) are never read                                */
     const float* logp;           /* [n_agents, rows] current log-probs (iplan_ac_fwd output)         */
     const float* entropy;        /* [n_agents, rows]                                                 */
     const float* values;         /* [n_agents, rows] current values                                  */

@@ -175,6 +175,8 @@ extern "C" int iplan_ppo_loss(const IplanPpoLossArgs* a, iplan_stream_t stream) 
     if (!a || a->n_agents < 1 || a->rows < 1 || !a->logp || !a->entropy || !a->values || !a->old_logp || !a->adv ||
         !a->value_preds || !a->returns || !a->mask || !a->g_logp || !a->g_values || !a->stats)
         return fail(IPLAN_EINVAL, "iplan_ppo_loss: bad arguments");
+    if ((int64_t)a->rows > a->row_stride)
+        return fail(IPLAN_EINVAL, "iplan_ppo_loss: rows %d > row_stride %lld (would read the next agent's rows)", a->rows, (long long)a->row_stride);
     if (a->n_parts > 1 && (!a->mask_sum || a->n_parts > 1024))
         return fail(IPLAN_EINVAL, "iplan_ppo_loss: n_parts > 1 needs mask_sum (and at most 1024 parts)");
     hipLaunchKernelGGL(ppo_loss_kernel, dim3((unsigned)a->n_agents, (unsigned)(a->n_parts > 1 ? a->n_parts : 1)), dim3(1024), 0, (hipStream_t)stream, *a);
@@ -185,6 +187,8 @@ extern "C" int iplan_ppo_adv_norm(const IplanAdvNormArgs* a, iplan_stream_t stre
     using namespace iplan;
     if (!a || a->n_agents < 1 || a->n < 1 || !a->adv || !a->sum || !a->sqdev || a->phase < 0 || a->phase > 2 || !(a->count >= 2.0f))
         return fail(IPLAN_EINVAL, "iplan_ppo_adv_norm: bad arguments");
+    if ((int64_t)a->n > a->row_stride)
+        return fail(IPLAN_EINVAL, "iplan_ppo_adv_norm: n %d > row_stride %lld (would write the next agent's rows)", a->n, (long long)a->row_stride);
     hipLaunchKernelGGL(adv_norm_kernel, dim3((unsigned)a->n_agents), dim3(1024), 0, (hipStream_t)stream, *a);
     return check_launch("iplan_ppo_adv_norm");
 }
