@@ -1205,6 +1205,15 @@ int iplan_mlp3_bwd(const IplanMlp3Args* args, iplan_stream_t stream);
  * nn.GRU semantics, batch_first, `layers` stacked layers (1..4) of width H in {32, 64}; rows = N*V.  Inference only.
  * enc_off / dec_off: per layer l  [4l + 0..3] = weight_ih_l<l> [3H, In_l], weight_hh_l<l> [3H, H], bias_ih_l<l>, bias_hh_l<l>
  * (In_0 = input_size for the encoder, output_size for the decoder; In_l = H above); lin_off = decoder.linear.weight [O, H], .bias.
+ * Alignment: `params` is 16-byte aligned and every weight_hh offset (enc_off / dec_off [4l + 1], l < layers) is a multiple of 4 floats
+ * -- their fragments are unconditional 16-byte loads; refused otherwise.  Every other offset, and the base of x, last, teacher, keep,
+ * out, hidden_out, save, g_out and dsave, needs only the 4 bytes of a float: where an address is not 16-byte aligned the kernels take
+ * their scalar path and move the same values.  Offsets are not range-checked against the block.
+ * Refused with IPLAN_EINVAL (both entry points check the forward's descriptor alike): dims outside 1 <= In <= 64, 1 <= O <= 16,
+ * H in {32, 64}, 1 <= layers <= 4, rows, T_in, P >= 1; a NULL x, last, params or out (the backward: save, params, g_out, dsave);
+ * `keep` with drop_p outside [0, 1) or NaN; `teacher` without `coins` or `coins` without `teacher`.
+ * Not refused: drop_p is ignored (any value) when `keep` is NULL; teacher[:, t] is read only where coins[t] != 0, and the cell of the
+ * last step feeds nothing; nothing behind the last row of any tensor is read or written.
  */
 #define IPLAN_S2S_MAX_LAYERS 4
 typedef struct {

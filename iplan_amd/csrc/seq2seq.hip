@@ -199,14 +199,31 @@ __global__ __launch_bounds__(256) void seq2seq_bwd_kernel(IplanSeq2SeqBwdArgs b)
 
 }  // namespace iplan
 
+// What both launchers ask of the forward's descriptor (include/iplan_hip.h lists the same conditions)
+static int seq2seq_check(const char* who, const IplanSeq2SeqArgs* a) {
+    using namespace iplan;
+    if (a->rows < 1 || a->T_in < 1 || a->In < 1 || a->In > 64 || a->layers < 1 || a->layers > IPLAN_S2S_MAX_LAYERS || a->P < 1 ||
+        a->O < 1 || a->O > 16 || (a->H != 32 && a->H != 64))
+        return fail(IPLAN_EINVAL, "%s: unsupported dims rows=%d T=%d In=%d H=%d layers=%d P=%d O=%d (In <= 64, O <= 16, H in {32, 64})", who,
+                    a->rows, a->T_in, a->In, a->H, a->layers, a->P, a->O);
+    if (!a->params) return fail(IPLAN_EINVAL, "%s: null tensor pointer", who);
+    // the kernels divide by 1 - drop_p wherever keep is given (written so that a NaN is refused too)
+    if (a->keep && !(a->drop_p >= 0.f && a->drop_p < 1.f)) return fail(IPLAN_EINVAL, "%s: dropout p=%f", who, a->drop_p);
+    if (!a->teacher != !a->coins) return fail(IPLAN_EINVAL, "%s: teacher and coins go together (one of them is NULL)", who);
+    // weight_hh fragments are unconditional 16-byte loads (wfrag_a)
+    if (((uintptr_t)a->params & 15) != 0) return fail(IPLAN_EINVAL, "%s: params is not 16-byte aligned", who);
+    for (int L = 0; L < a->layers; ++L)
+        if ((a->enc_off[4 * L + 1] & 3) != 0 || (a->dec_off[4 * L + 1] & 3) != 0)
+            return fail(IPLAN_EINVAL, "%s: weight_hh_l%d offset is not a multiple of 4 floats", who, L);
+    return IPLAN_OK;
+}
+
 extern "C" int iplan_seq2seq_bwd(const IplanSeq2SeqBwdArgs* b, iplan_stream_t stream) {
     using namespace iplan;
     if (!b) return fail(IPLAN_EINVAL, "iplan_seq2seq_bwd: null args");
     const IplanSeq2SeqArgs* a = &b->fwd;
-    if (a->rows < 1 || a->T_in < 1 || a->In < 1 || a->In > 64 || a->layers < 1 || a->layers > IPLAN_S2S_MAX_LAYERS || a->P < 1 ||
-        a->O < 1 || a->O > 16 || (a->H != 32 && a->H != 64))
-        return fail(IPLAN_EINVAL, "iplan_seq2seq_bwd: unsupported dims");
-    if (!a->save || !a->params || !b->g_out || !b->dsave) return fail(IPLAN_EINVAL, "iplan_seq2seq_bwd: the forward launch did not save its record, or null tensor pointer");
+    if (const int rc = seq2seq_check("iplan_seq2seq_bwd", a)) return rc;
+    if (!a->save || !b->g_out || !b->dsave) return fail(IPLAN_EINVAL, "iplan_seq2seq_bwd: the forward launch did not save its record, or null tensor pointer");
     const dim3 grid((unsigned)((a->rows + 63) / 64));
     const size_t lds = (size_t)4 * a->layers * (a->H / 16) * 64 * 16;      // the carry: <= 64 KiB
     if (a->H == 32) hipLaunchKernelGGL(seq2seq_bwd_kernel<2>, grid, dim3(256), lds, (hipStream_t)stream, *b);
@@ -217,12 +234,8 @@ extern "C" int iplan_seq2seq_bwd(const IplanSeq2SeqBwdArgs* b, iplan_stream_t st
 extern "C" int iplan_seq2seq_fwd(const IplanSeq2SeqArgs* a, iplan_stream_t stream) {
     using namespace iplan;
     if (!a) return fail(IPLAN_EINVAL, "iplan_seq2seq_fwd: null args");
-    if (a->rows < 1 || a->T_in < 1 || a->In < 1 || a->In > 64 || a->layers < 1 || a->layers > IPLAN_S2S_MAX_LAYERS || a->P < 1 ||
-        a->O < 1 || a->O > 16 || (a->H != 32 && a->H != 64))
-        return fail(IPLAN_EINVAL, "iplan_seq2seq_fwd: unsupported dims rows=%d T=%d In=%d H=%d layers=%d P=%d O=%d (In <= 64, O <= 16, H in {32, 64})",
-                    a->rows, a->T_in, a->In, a->H, a->layers, a->P, a->O);
-    if (!a->x || !a->last || !a->params || !a->out) return fail(IPLAN_EINVAL, "iplan_seq2seq_fwd: null tensor pointer");
-    if (a->keep && (a->drop_p < 0.f || a->drop_p >= 1.f)) return fail(IPLAN_EINVAL, "iplan_seq2seq_fwd: dropout p=%f", a->drop_p);
+    if (const int rc = seq2seq_check("iplan_seq2seq_fwd", a)) return rc;
+    if (!a->x || !a->last || !a->out) return fail(IPLAN_EINVAL, "iplan_seq2seq_fwd: null tensor pointer");
     const dim3 grid((unsigned)((a->rows + 63) / 64));
     if (a->H == 32) hipLaunchKernelGGL(seq2seq_fwd_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, *a);
     else hipLaunchKernelGGL(seq2seq_fwd_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, *a);

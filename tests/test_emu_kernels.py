@@ -376,6 +376,7 @@ def check_seq2seq_shapes_vs_oracle(device, cases=None):
     import numpy as np
     from oracle import iplan_oracle as O
     from iplan_amd.nova.Seq2Seq import Seq2Seq
+    from tests.oracle_checks import E32_FACTOR, _grad_err
     #         C   H  layers P  O   R  T  ratio train teacher
     cases = cases or [(64, 64, 4, 3, 16, 21, 2, 0.0, True, True), (3, 32, 3, 1, 1, 16, 1, 1.0, True, True), (5, 32, 2, 5, 2, 7, 3, 0.5, False, True),
                       (4, 64, 1, 4, 2, 33, 4, 0.5, True, False)]
@@ -389,20 +390,27 @@ def check_seq2seq_shapes_vs_oracle(device, cases=None):
         teacher = torch.rand(R, P, No, generator=gen) * 2 - 1 if with_teacher else None
         gw = torch.rand(R, P, No, generator=gen) * 2 - 1
         keep = (torch.rand(P, R, H, generator=gen) > 0.25).float()
-        p64 = {k: v.detach().cpu().double().clone().requires_grad_(True) for k, v in net.state_dict().items()}
         np.random.seed(300 + i)
         coins = [bool(np.random.random() < ratio) for _ in range(P)]
-        o64 = O.seq2seq_forward(p64, x.double(), last.double(), P, teacher.double() if with_teacher else None, coins,
-                                keep.double().reshape(P, R, 1, H) if train else None, 0.25)
-        (o64 * gw.double()).sum().backward()
+        ref = {}
+        for dt in (torch.float64, torch.float32):
+            prm = {k: v.detach().cpu().to(dt).clone().requires_grad_(True) for k, v in net.state_dict().items()}
+            o = O.seq2seq_forward(prm, x.to(dt), last.to(dt), P, teacher.to(dt) if with_teacher else None, coins,
+                                  keep.to(dt).reshape(P, R, 1, H) if train else None, 0.25)
+            (o * gw.to(dt)).sum().backward()
+            ref[dt] = (o.detach(), prm)
+        o64, p64 = ref[torch.float64]
         np.random.seed(300 + i)
         out = net(x.to(device), last.to(device), teacher.to(device) if with_teacher else None, keep=keep.to(device))
         tag = (C, H, layers, P, No, R, T, ratio, train, with_teacher)
-        assert rel_err(out.detach().cpu(), o64.detach().float()) < 1e-5, (tag, rel_err(out.detach().cpu(), o64.detach().float()))
+        assert rel_err(out.detach().cpu(), o64.float()) < 1e-5, (tag, rel_err(out.detach().cpu(), o64.float()))
         (out * gw.to(device)).sum().backward()
+        # every parameter gradient on its OWN scale, bound = max(1e-5, E32_FACTOR x the fp32 oracle's error by
+        # the same measure): the tensors peak at 1e-2 .. 5e-2, where rel_err's max(1, .) forgave 0.1 % of a tensor's size
         for k, q in net.named_parameters():
-            e = rel_err(q.grad.cpu(), p64[k].grad.float())
-            assert e < 1e-5, (tag, k, e)
+            e, e32 = _grad_err(q.grad, p64[k].grad), _grad_err(ref[torch.float32][1][k].grad, p64[k].grad)
+            print("seq2seq shapes", tag, k, "err", e, "e32", e32)
+            assert e <= max(1e-5, E32_FACTOR * e32), (tag, k, e, e32)
 
 
 def test_seq2seq_limit_shapes_vs_oracle_emulated():
